@@ -2,9 +2,18 @@
 """Headline benchmark: fp64 TFLOP/s (whole node) for dgemm / dpotrf / dgetrf /
 dgeqrf at n = 65536 on N MI355X GPUs (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set up, W warmup and K
+timed steps of the four routines, the JSON line.  `--full` adds everything
+else: the backward-error check of every routine (`--check`) and the
+BASELINE.json configs beyond the suite (`--extras`, reported under "configs").
+`--dump-outputs DIR` writes what the last timed step of every suite routine
+returned to DIR/<routine>_<what>.npy (float64; a fixed, seeded sample of the
+rows and columns of each matrix, the same in every run), so that two builds
+can be compared output for output: the inputs depend on the arguments only.
 
 One process per GPU; a p x q process grid (1x1, 1x2, 2x2, 2x4 by default)
 with RCCL communicators.  Each step runs every routine once on a freshly
@@ -151,9 +160,19 @@ def parse():
     ap.add_argument("--trace", default="")
     ap.add_argument("--mixed-escalate", default="yes", choices=["yes", "no"],
                     help="dgesv_mixed: GMRES-IR escalation before the fp64 fallback (no = reference semantics)")
-    ap.add_argument("--extras", default="all", help="BASELINE configs to add after the suite: all, none, or names")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the backward-error checks (--check) "
+                         "and the BASELINE configs beyond the suite (--extras)")
+    ap.add_argument("--target", default="auto", choices=["auto", "d", "h"],
+                    help="auto: the device when one is visible, else the host; h: the host target and host "
+                         "communicators even where a GPU is visible")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step of each suite routine returned to DIR/<name>.npy")
+    ap.add_argument("--extras", default="all",
+                    help="with --full: BASELINE configs to add after the suite: all, none, or names")
     ap.add_argument("--check", default="yes", choices=["yes", "no"],
-                    help="backward-error check of each routine after its timed steps (outside the timed region)")
+                    help="with --full: backward-error check of each routine after its timed steps (outside the "
+                         "timed region)")
     ap.add_argument("--extras-steps", type=int, default=2, help="timed steps per BASELINE extra config")
     ap.add_argument("--extras-warmup", type=int, default=1, help="warmup steps per BASELINE extra config")
     ap.add_argument("--time-budget", type=float, default=555.0,
@@ -262,7 +281,9 @@ def main(a):
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     if s.device_available():
         s._slate.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, s._slate.device_count()))
-    target = "d" if s.device_available() else "h"
+    target = ("d" if s.device_available() else "h") if a.target == "auto" else a.target
+    if target == "h":
+        os.environ["SLATE_COMM"] = "host"   # init_grid: no RCCL communicators for a host-target job
     p, q = (a.p, a.q) if a.p and a.q else s.choose_grid(world)
     wd = Watchdog(rank)
     wd.arm("init_grid")
@@ -392,6 +413,46 @@ def main(a):
         del A0
         return err
 
+    # --dump-outputs: at most DUMP_K x DUMP_K elements per matrix and rank (8 MB
+    # in float64 on one GPU; five matrices and the pivots stay under 64 MB)
+    DUMP_K = int(1024 / np.sqrt(world))
+
+    def dump_matrix(name, M, tg, lower=False):
+        """Save a sample of this rank's local block of M: the rows and columns
+        drawn by a generator seeded with 0 (the whole block when it has at most
+        DUMP_K of them), read where the block lives, so a device matrix is not
+        copied to the host.  lower: entries above the diagonal (which potrf
+        does not define) are saved as zero."""
+        import torch
+        t = s.local_tensor(M, device=(tg == "d"))
+        rng = np.random.default_rng(0)
+        pick = [np.arange(sz) if sz <= DUMP_K else np.sort(rng.choice(sz, DUMP_K, replace=False)) for sz in t.shape]
+        ri, ci = (torch.from_numpy(p).to(t.device) for p in pick)
+        out = t[ri[:, None], ci[None, :]].cpu().numpy().astype(np.float64)
+        if lower:
+            gr = np.asarray(M.local_row_indices(), dtype=np.int64)[pick[0]]
+            gc = np.asarray(M.local_col_indices(), dtype=np.int64)[pick[1]]
+            out[gr[:, None] < gc[None, :]] = 0.0
+        sfx = f"_rank{rank}" if world > 1 else ""
+        np.save(os.path.join(a.dump_outputs, f"{name}{sfx}.npy"), out)
+
+    def dump_outputs(rname, mats, tg):
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        if rname == "dgemm":
+            dump_matrix("dgemm_C", mats["C"], tg)
+        elif rname == "dpotrf":
+            dump_matrix("dpotrf_L", mats["A"], tg, lower=True)
+        elif rname == "dgetrf":
+            dump_matrix("dgetrf_LU", mats["A"], tg)
+            if rank == 0:   # the pivots are replicated: (tile index, offset) per row
+                piv = np.array([x for blk in mats["piv"] for x in blk], dtype=np.float64).reshape(-1, 2)
+                np.save(os.path.join(a.dump_outputs, "dgetrf_piv.npy"), piv)
+        elif rname == "dgeqrf":
+            dump_matrix("dgeqrf_QR", mats["A"], tg)
+            if rank == 0:   # the T factors are replicated
+                for i, Tf in enumerate(mats["T"]):
+                    dump_matrix(f"dgeqrf_T{i}", Tf, tg)
+
     def run(rname, n_, nb, tg, label, warmup=None, steps=None, deadline=None):
         """W untimed + K timed steps of one routine; returns its result dict.
         With a deadline (extras only) the timed steps are cut to what fits
@@ -501,7 +562,9 @@ def main(a):
         res = {"ms": t * 1e3, "tflops": flops / t / 1e12, "flops": flops, "nb": nb, "n": n_,
                "grid": f"{grid_r.p}x{grid_r.q}", "lookahead": la_of(rname),
                "steps": len(times), "warmup": warmup}
-        if a.check == "yes":
+        if a.dump_outputs and label == rname:   # the headline suite only
+            dump_outputs(rname, mats, tg)
+        if a.full and a.check == "yes":
             wd.arm(f"{label} residual check")
             err = residual(rname, mats, kind, seed, nb, n_, tg, grid_r)
             wd.disarm()
@@ -520,7 +583,7 @@ def main(a):
     for rname in routines:
         results[rname] = run(rname, n, nb_per.get(rname, a.nb), target, rname)
     configs = {}
-    extras = list(EXTRAS) if a.extras == "all" else ([] if a.extras == "none" else a.extras.split(","))
+    extras = [] if not a.full or a.extras == "none" else (list(EXTRAS) if a.extras == "all" else a.extras.split(","))
     # per-flop time of the slowest suite routine: first-step estimate for an extra
     rate = max((r["ms"] / 1e3 / r["flops"] for r in results.values()), default=0.0)
     for name in extras:
@@ -577,6 +640,7 @@ def main(a):
                          for kk, vv in v.items() if kk != "flops"} for k, v in results.items()},
         "configs": {k: {kk: (round(vv, 4) if isinstance(vv, float) and kk != "backward_error" else vv)
                         for kk, vv in v.items() if kk != "flops"} for k, v in configs.items()},
+        "full": bool(a.full),
         "wall_s": round(time.time() - _T_START, 1),
     }
     if rank == 0:
