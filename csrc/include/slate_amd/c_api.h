@@ -27,9 +27,18 @@ enum {
     slate_Option_InnerBlocking = 3, slate_Option_MaxPanelThreads = 4, slate_Option_Tolerance = 5,
     slate_Option_Target = 6, slate_Option_HoldLocalWorkspace = 7, slate_Option_Depth = 8,
     slate_Option_MaxIterations = 9, slate_Option_UseFallbackSolver = 10, slate_Option_PivotThreshold = 11,
+    slate_Option_EscalateGmres = 12, slate_Option_GemmPrecision = 13,
     slate_Option_MethodCholQR = 60, slate_Option_MethodEig = 61, slate_Option_MethodGels = 62,
     slate_Option_MethodGemm = 63, slate_Option_MethodHemm = 64, slate_Option_MethodLU = 65,
     slate_Option_MethodTrsm = 66
+};
+
+/* ivalue of slate_Option_GemmPrecision (slate::GemmPrecision): arithmetic of
+ * the fp32 trailing updates of gemm, the LU family and Cholesky; the mixed
+ * solvers apply it to their fp32 factorization */
+enum {
+    slate_GemmPrecision_Native = 78, slate_GemmPrecision_BF16 = 49, slate_GemmPrecision_BF16x3 = 51,
+    slate_GemmPrecision_BF16x6 = 54
 };
 
 typedef struct {

@@ -43,6 +43,11 @@ enum class LayoutConvert : char { ColMajor = 'C', RowMajor = 'R', None = 'N' };
 /// Eigenvalue method (enums.hh MethodEig).
 enum class MethodEig : char { QR = 'Q', DC = 'D' };
 
+/// Arithmetic of the large device fp32 products (trailing updates) of a
+/// routine: the fp32 MFMA kernels, or the split-operand bf16 MFMA kernel with
+/// 1, 3 or 6 plane products per K-step (gemm_bf16s.hip).  Not in the reference.
+enum class GemmPrecision : char { Native = 'N', BF16 = '1', BF16x3 = '3', BF16x6 = '6' };
+
 /// Keys for options passed to routines (enums.hh:63-99).
 enum class Option : char {
     ChunkSize,
@@ -63,6 +68,10 @@ enum class Option : char {
     /// full-precision fallback.  Not in the reference (default off: the
     /// reference semantics, classical refinement then fallback).
     EscalateGmres,
+    /// GemmPrecision of the fp32 trailing updates (gemm, getrf family, potrf;
+    /// the mixed solvers apply it to their low-precision factorization only).
+    /// Default Native.  Not in the reference.
+    GemmPrecision,
 
     PrintVerbose = 50,
     PrintEdgeItems,
@@ -114,5 +123,8 @@ const char* to_string(Uplo v);
 const char* to_string(Norm v);
 Target str2target(const std::string& s);
 Norm   str2norm(const std::string& s);
+const char* to_string(GemmPrecision p);
+/// "native", "bf16", "bf16x3", "bf16x6"; anything else throws.
+GemmPrecision str2gemm_precision(const std::string& s);
 
 }  // namespace slate

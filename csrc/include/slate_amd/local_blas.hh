@@ -57,6 +57,32 @@ struct PackAHint {
     PackAHint& operator=(PackAHint const&) = delete;
 };
 
+/// While a non-Native scope is alive on this thread, device gemm<float> and
+/// gemm_tri<float> (so herk / syrk<float> too) run products with m, n >= 128,
+/// k >= 32 that the fp32 dispatcher would not split over K on the
+/// split-operand bf16 MFMA kernel (gemm_bf16s.hip).  Everything else -- panels,
+/// leaves, gemv-path products, split-K products, the p x q Cholesky staircase
+/// update, other types, the host target -- is unchanged.  Drivers enqueue from
+/// the calling thread; in-process ranks open the scope on their own thread.
+struct GemmPrecisionScope {
+    explicit GemmPrecisionScope(GemmPrecision p);
+    ~GemmPrecisionScope();
+    GemmPrecisionScope(GemmPrecisionScope const&) = delete;
+    GemmPrecisionScope& operator=(GemmPrecisionScope const&) = delete;
+private:
+    GemmPrecision prev_;
+};
+/// Option::GemmPrecision of opts (default Native); a value outside the enum
+/// throws slate::Exception.
+GemmPrecision gemm_precision_option(Options const& opts);
+/// Launches of the split-operand bf16 kernel in this process so far.
+uint64_t lowprec_gemm_calls();
+/// The raw kernel: C = alpha op(A) op(B) + beta C on device fp32 data, any
+/// shape; uplo General, or Lower / Upper for that triangle of a square C.
+void gemm_lowprec(Ctx const& c, GemmPrecision p, Uplo uplo, Op opA, Op opB, int64_t m, int64_t n, int64_t k,
+                  float alpha, float const* A, int64_t lda, float const* B, int64_t ldb, float beta, float* C,
+                  int64_t ldc);
+
 template <typename T>
 void gemm(Ctx const& c, Op opA, Op opB, int64_t m, int64_t n, int64_t k, T alpha,
           T const* A, int64_t lda, T const* B, int64_t ldb, T beta, T* C, int64_t ldc);

@@ -219,6 +219,13 @@ struct StairMap {
 template <typename T>
 void gemm_stair_real(int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B, int64_t ldb,
                      StairMap const& sm, T beta, T* C, int64_t ldc, hipStream_t stream);
+/// Split-operand bf16 MFMA product on fp32 data (gemm_bf16s.hip): each operand
+/// is split into nsplit (1, 2 or 3) bf16 planes as it is staged and the plane
+/// products (i, j) with i + j < nsplit are accumulated in fp32.  uplo 'G': full
+/// C; 'L' / 'U': only that triangle of a square C.  Contract of gemm_real<float>.
+void gemm_bf16s(int nsplit, char uplo, char transA, char transB, int64_t m, int64_t n, int64_t k,
+                float alpha, const float* A, int64_t lda, const float* B, int64_t ldb,
+                float beta, float* C, int64_t ldc, hipStream_t stream);
 template <typename T>
 void gemm_cplx(char uplo, char transA, char transB, int64_t m, int64_t n, int64_t k,
                T alpha, const T* A, int64_t lda, const T* B, int64_t ldb,

@@ -156,6 +156,10 @@ Options to_options(py::dict d) {
         else if (k == "max_iterations") o[Option::MaxIterations] = v.cast<int64_t>();
         else if (k == "use_fallback_solver") o[Option::UseFallbackSolver] = v.cast<bool>();
         else if (k == "escalate_gmres") o[Option::EscalateGmres] = int64_t(v.cast<bool>());
+        else if (k == "gemm_precision") {
+            if (py::isinstance<py::str>(v)) o[Option::GemmPrecision] = str2gemm_precision(v.cast<std::string>());
+            else o[Option::GemmPrecision] = v.cast<int64_t>();
+        }
         else if (k == "pivot_threshold") o[Option::PivotThreshold] = v.cast<double>();
         else if (k == "hold_local_workspace") o[Option::HoldLocalWorkspace] = v.cast<bool>();
         else if (k == "depth") o[Option::Depth] = v.cast<int64_t>();
@@ -529,6 +533,19 @@ PYBIND11_MODULE(_slate, m) {
     m.def("get_device", &device::get_device);
     m.def("sync", &slate::sync, py::call_guard<py::gil_scoped_release>());
     m.def("set_ops_queue", [](int q) { ops_queue() = q; });
+    // the split-operand bf16 MFMA kernel on device pointers (fp32 data)
+    m.def("lb_gemm_lowprec", [](std::string mode, std::string up, std::string ta, std::string tb, int64_t mm, int64_t n,
+                                int64_t k, float a, uintptr_t A, int64_t lda, uintptr_t B, int64_t ldb, float b,
+                                uintptr_t C, int64_t ldc) {
+        const GemmPrecision p = str2gemm_precision(mode);
+        const Uplo u = up == "L" ? Uplo::Lower : up == "U" ? Uplo::Upper : Uplo::General;
+        py::gil_scoped_release r;
+        auto c = lb::Ctx::device(ops_queue());
+        lb::gemm_lowprec(c, p, u, ta == "N" ? Op::NoTrans : Op::Trans, tb == "N" ? Op::NoTrans : Op::Trans, mm, n, k, a,
+                         (float const*)A, lda, (float const*)B, ldb, b, (float*)C, ldc);
+        slate_hip_call(hipStreamSynchronize(c.stream));
+    });
+    m.def("lowprec_gemm_calls", &lb::lowprec_gemm_calls);
     m.def("queue_sync", [](int q) { slate_hip_call(hipStreamSynchronize(device::queue(q))); },
           py::call_guard<py::gil_scoped_release>());
     m.def("release_cache", &device::release_cache);

@@ -123,6 +123,7 @@ template <typename T>
 void gemmC(T alpha, Matrix<T> const& A_in, Matrix<T> const& B_in, T beta, Matrix<T>& C, Options const& opts) {
     trace::Block tb("gemmC");
     internal::DriverScope ds_;
+    lb::GemmPrecisionScope gp_(internal::driver_gemm_precision<T>(opts));
     Target target = resolve_target(opts);
     const int64_t la = option_la(opts);
     slate_error_if_msg(A_in.m() != C.m() || B_in.n() != C.n() || A_in.n() != B_in.m(), "gemm: dimension mismatch");
@@ -256,6 +257,7 @@ template <typename T>
 void gemmA(T alpha, Matrix<T> const& A_in, Matrix<T> const& B_in, T beta, Matrix<T>& C, Options const& opts) {
     trace::Block tb("gemmA");
     internal::DriverScope ds_;
+    lb::GemmPrecisionScope gp_(internal::driver_gemm_precision<T>(opts));
     Target target = resolve_target(opts);
     auto gC = C.grid();
     if (gC->size() == 1) { gemmC(alpha, A_in, B_in, beta, C, opts); return; }

@@ -53,6 +53,25 @@ Target str2target(const std::string& s_) {
     throw Exception("unknown target: " + s_);
 }
 
+GemmPrecision str2gemm_precision(const std::string& s_) {
+    std::string s = s_;
+    std::transform(s.begin(), s.end(), s.begin(), ::tolower);
+    if (s == "native") return GemmPrecision::Native;
+    if (s == "bf16") return GemmPrecision::BF16;
+    if (s == "bf16x3") return GemmPrecision::BF16x3;
+    if (s == "bf16x6") return GemmPrecision::BF16x6;
+    throw Exception("unknown gemm precision: " + s_);
+}
+
+const char* to_string(GemmPrecision p) {
+    switch (p) {
+        case GemmPrecision::BF16:   return "bf16";
+        case GemmPrecision::BF16x3: return "bf16x3";
+        case GemmPrecision::BF16x6: return "bf16x6";
+        default:                    return "native";
+    }
+}
+
 Norm str2norm(const std::string& s_) {
     std::string s = s_;
     std::transform(s.begin(), s.end(), s.begin(), ::tolower);

@@ -796,6 +796,7 @@ template <typename T>
 int64_t getrf_impl(Matrix<T>& A_in, Pivots& pivots, Options const& opts, PanelMode mode) {
     trace::Block tb("getrf");
     internal::DriverScope ds_;
+    lb::GemmPrecisionScope gp_(internal::driver_gemm_precision<T>(opts));
     Target target = resolve_target(opts);
     const int64_t la = get_option<int64_t>(opts, Option::Lookahead, 1);
     const double thresh = pivot_threshold(opts);

@@ -214,6 +214,8 @@ int64_t gesv_mixed_gmres(Matrix<T>& A, Pivots& pivots, Matrix<T>& B, Matrix<T>& 
     }
     trace::Block tb("gesv_mixed_gmres");
     internal::DriverScope ds_;
+    // Option::GemmPrecision reaches the fp32 factorization through opts
+    internal::check_mixed_gemm_precision<T>(opts, "gesv_mixed_gmres");
     using Lo = typename lower_prec<T>::type;
     slate_error_if_msg(B.n() != 1, "gesv_mixed_gmres: one right-hand side");
     Target target = resolve_target(opts);
@@ -272,6 +274,8 @@ int64_t posv_mixed_gmres(HermitianMatrix<T>& A, Matrix<T>& B, Matrix<T>& X, int&
     }
     trace::Block tb("posv_mixed_gmres");
     internal::DriverScope ds_;
+    // Option::GemmPrecision reaches the fp32 factorization through opts
+    internal::check_mixed_gemm_precision<T>(opts, "posv_mixed_gmres");
     using Lo = typename lower_prec<T>::type;
     slate_error_if_msg(B.n() != 1, "posv_mixed_gmres: one right-hand side");
     Target target = resolve_target(opts);

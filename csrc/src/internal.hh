@@ -121,6 +121,21 @@ inline Target resolve_target(Options const& opts) {
     return t;
 }
 
+/// Option::GemmPrecision as a driver on scalar type T applies it: the value is
+/// checked for every type and in effect for float only.
+template <typename T>
+inline GemmPrecision driver_gemm_precision(Options const& opts) {
+    const GemmPrecision p = lb::gemm_precision_option(opts);
+    return std::is_same_v<T, float> ? p : GemmPrecision::Native;
+}
+/// Mixed-precision drivers on working type T: the option goes to the fp32
+/// factorization; a complex working type has no bf16 path to give it to.
+template <typename T>
+inline void check_mixed_gemm_precision(Options const& opts, char const* name) {
+    if (lb::gemm_precision_option(opts) != GemmPrecision::Native && is_complex_v<T>)
+        slate_not_implemented(std::string(name) + ": Option::GemmPrecision needs a real matrix type");
+}
+
 /// Driver nesting depth on this thread.  Option::HoldLocalWorkspace = false
 /// (the default, reference src/potrf.cc:42,198) frees a matrix's non-origin
 /// instance -- the device copy of a host-origin matrix, i.e. SLATE's

@@ -4,6 +4,7 @@
 #include "../kernels/kernels.hh"
 #include "slate_amd/eig_host.hh"
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <cstring>
@@ -146,6 +147,48 @@ inline bool pack_a_form(int64_t m, int64_t n, int64_t k) {
 }  // namespace
 slate::lb::PackAHint::PackAHint() { ++t_pack_a_hint; }
 slate::lb::PackAHint::~PackAHint() { --t_pack_a_hint; }
+
+//------------------------------------------------------------------------------
+// Low-precision (split-operand bf16) products
+namespace {
+thread_local GemmPrecision t_gemm_precision = GemmPrecision::Native;
+std::atomic<uint64_t> g_lowprec_calls{0};
+
+inline int nsplit_of(GemmPrecision p) {
+    switch (p) {
+        case GemmPrecision::BF16:   return 1;
+        case GemmPrecision::BF16x3: return 2;
+        case GemmPrecision::BF16x6: return 3;
+        default:                    return 0;
+    }
+}
+}  // namespace
+slate::lb::GemmPrecisionScope::GemmPrecisionScope(GemmPrecision p) : prev_(t_gemm_precision) { t_gemm_precision = p; }
+slate::lb::GemmPrecisionScope::~GemmPrecisionScope() { t_gemm_precision = prev_; }
+
+GemmPrecision gemm_precision_option(Options const& opts) {
+    const int64_t v = get_option<int64_t>(opts, Option::GemmPrecision, int64_t(GemmPrecision::Native));
+    if (v != int64_t(GemmPrecision::Native) && v != int64_t(GemmPrecision::BF16) &&
+        v != int64_t(GemmPrecision::BF16x3) && v != int64_t(GemmPrecision::BF16x6))
+        slate_error("Option::GemmPrecision: value " + std::to_string(v) + " is not a GemmPrecision");
+    return GemmPrecision(char(v));
+}
+
+uint64_t lowprec_gemm_calls() { return g_lowprec_calls.load(std::memory_order_relaxed); }
+
+void gemm_lowprec(Ctx const& c, GemmPrecision p, Uplo uplo, Op opA, Op opB, int64_t m, int64_t n, int64_t k,
+                  float alpha, float const* A, int64_t lda, float const* B, int64_t ldb, float beta, float* C,
+                  int64_t ldc) {
+    const int ns = nsplit_of(p);
+    slate_error_if_msg(ns == 0, "gemm_lowprec: precision must be BF16, BF16x3 or BF16x6");
+    slate_error_if_msg(!c.dev(), "gemm_lowprec: device target only");
+    slate_error_if_msg(uplo != Uplo::General && m != n, "gemm_lowprec: a triangular C must be square");
+    if (m <= 0 || n <= 0) return;
+    g_lowprec_calls.fetch_add(1, std::memory_order_relaxed);
+    kd::gemm_bf16s(ns, char(uplo), opA == Op::NoTrans ? 'N' : 'T', opB == Op::NoTrans ? 'N' : 'T', m, n, k, alpha, A,
+                   lda, B, ldb, beta, C, ldc, c.stream);
+}
+
 namespace {
 // SLATE_UPDATE_NT=0 keeps NN products in NN form (as internal::update_nt)
 inline bool nt_pack() {
@@ -157,10 +200,20 @@ inline bool nt_pack() {
 }
 
 // device gemm dispatch (real -> MFMA, complex -> complex kernel)
+// lowprec: the caller is lb::gemm / lb::gemm_tri, whose eligible fp32 products
+// follow the thread's GemmPrecisionScope
 template <typename T>
 void dgemm(hipStream_t s, char uplo, Op opA, Op opB, int64_t m, int64_t n, int64_t k, T alpha,
-           T const* A, int64_t lda, T const* B, int64_t ldb, T beta, T* C, int64_t ldc) {
+           T const* A, int64_t lda, T const* B, int64_t ldb, T beta, T* C, int64_t ldc, bool lowprec = false) {
     if (m <= 0 || n <= 0) return;
+    if constexpr (std::is_same_v<T, float>) {
+        if (lowprec && t_gemm_precision != GemmPrecision::Native && m >= 128 && n >= 128 && k >= 32 &&
+            !(ceildiv(m, 128) * ceildiv(n, 128) < 128 && k >= 1024)) {
+            gemm_lowprec(Ctx{Target::Devices, s}, t_gemm_precision, Uplo(uplo), opA, opB, m, n, k, alpha, A, lda, B,
+                         ldb, beta, C, ldc);
+            return;
+        }
+    }
     if constexpr (is_real_v<T>) {
         char ta = opA == Op::NoTrans ? 'N' : 'T', tb = opB == Op::NoTrans ? 'N' : 'T';
         // split-K for small outputs with a long K (e.g. V^H C in QR panels):
@@ -283,7 +336,7 @@ void gemm(Ctx const& c, Op opA, Op opB, int64_t m, int64_t n, int64_t k, T alpha
         gemv(c, opA, m, k, n, alpha, A, lda, B, ldb, beta, C, ldc);
         return;
     }
-    dgemm(c.stream, 'G', opA, opB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
+    dgemm(c.stream, 'G', opA, opB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, true);
 }
 
 template <typename T>
@@ -331,7 +384,7 @@ void gemm_tri(Ctx const& c, Uplo uplo, Op opA, Op opB, int64_t n, int64_t k, T a
         if (opA == Op::ConjTrans) opA = Op::Trans;
         if (opB == Op::ConjTrans) opB = Op::Trans;
     }
-    dgemm(c.stream, upc(uplo), opA, opB, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
+    dgemm(c.stream, upc(uplo), opA, opB, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, true);
 }
 
 template <typename T>
@@ -630,6 +683,9 @@ void potrf(Ctx const& c, Uplo uplo, int64_t n, T* A, int64_t lda, int* info, int
         return;
     }
     constexpr int64_t NB0 = 64;
+    // the diagonal block is a panel: its inner herk updates stay fp32 under a
+    // driver's GemmPrecisionScope
+    GemmPrecisionScope native_(GemmPrecision::Native);
     // Two launches per leaf (sizeof(T) <= 8: the leaf kernel's per-lane row
     // fits in 128 VGPRs): factor + A21 solve in one kernel, then the trailing
     // triangle.  SLATE_POTRF_LEAF=0 keeps the inverse-based leaf.

@@ -510,6 +510,7 @@ int64_t potrf(HermitianMatrix<T>& A_in, Options const& opts) {
     }
     trace::Block tb("potrf");
     internal::DriverScope ds_;
+    lb::GemmPrecisionScope gp_(internal::driver_gemm_precision<T>(opts));
     Target target = internal::resolve_target(opts);
     int64_t la = get_option<int64_t>(opts, Option::Lookahead, 1);
     BaseMatrix<T> A = A_in;

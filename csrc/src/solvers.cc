@@ -424,6 +424,9 @@ int64_t gesv_mixed(Matrix<T>& A, Pivots& pivots, Matrix<T>& B, Matrix<T>& X, int
     }
     trace::Block tb("gesv_mixed");
     internal::DriverScope ds_;
+    // Option::GemmPrecision reaches the fp32 factorization (factor_lo) through
+    // opts; solves, residuals and the fallback do not open a precision scope
+    internal::check_mixed_gemm_precision<T>(opts, "gesv_mixed");
     using Lo = typename lower_prec<T>::type;
     if constexpr (std::is_same_v<Lo, T>) {
         slate_error("gesv_mixed requires a double-precision type");
@@ -454,6 +457,9 @@ int64_t posv_mixed(HermitianMatrix<T>& A, Matrix<T>& B, Matrix<T>& X, int& iter,
     }
     trace::Block tb("posv_mixed");
     internal::DriverScope ds_;
+    // Option::GemmPrecision reaches the fp32 factorization (factor_lo) through
+    // opts; solves, residuals and the fallback do not open a precision scope
+    internal::check_mixed_gemm_precision<T>(opts, "posv_mixed");
     using Lo = typename lower_prec<T>::type;
     if constexpr (std::is_same_v<Lo, T>) {
         slate_error("posv_mixed requires a double-precision type");

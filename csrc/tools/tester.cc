@@ -26,6 +26,7 @@
 #include <functional>
 #include <limits>
 #include <map>
+#include <set>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -53,6 +54,10 @@ struct Params {
     int64_t itermax = -1;
     int fallback = -1;
     double pivot_threshold = -1;
+    // --gemm-precision native|bf16|bf16x3|bf16x6: Option::GemmPrecision of gemm,
+    // the getrf family, potrf and the mixed solvers (unset: not passed)
+    bool has_gemm_precision = false;
+    GemmPrecision gemm_precision = GemmPrecision::Native;
     // operand shape flags of the BLAS-3 / triangular routines (reference
     // --uplo --trans --side --diag)
     Uplo uplo = Uplo::Lower;
@@ -1963,6 +1968,11 @@ int run_type(Params const& P, char tc, std::string const& name) {
         for (int64_t nb : P.nbs)
             for (int rep = 0; rep < P.repeat; ++rep) {
                 Case<T> c(P, d, nb);
+                static const std::set<std::string> takes_precision = {
+                    "gemm", "getrf", "getrf_tntpiv", "getrf_nopiv", "potrf", "gesv_mixed", "gesv_mixed_gmres",
+                    "posv_mixed", "posv_mixed_gmres"};
+                const bool with_precision = P.has_gemm_precision && takes_precision.count(name) > 0;
+                if (with_precision) c.opts[Option::GemmPrecision] = P.gemm_precision;
                 Result r;
                 std::string status;
                 try {
@@ -1982,10 +1992,12 @@ int run_type(Params const& P, char tc, std::string const& name) {
                     if (P.check && !r.skipped && !std::isnan(r.error)) std::snprintf(es, sizeof(es), "%10.2e", r.error);
                     else std::snprintf(es, sizeof(es), "%10s", "NA");
                     double gf = (r.time > 0 && r.flops > 0) ? r.flops / r.time / 1e9 : NAN;
-                    std::printf("%-16s %-4c %7lld %7lld %7lld %5lld %2d %2d %s %10.4f %11.2f  %s%s%s\n", name.c_str(), tc,
-                                (long long)c.m, (long long)c.n, (long long)c.k, (long long)nb, g->p(), g->q(), es,
+                    const std::string prec =
+                        with_precision ? std::string("  gemm_precision=") + to_string(P.gemm_precision) : "";
+                    std::printf("%-16s %-4c %7lld %7lld %7lld %5lld %2d %2d %s %10.4f %11.2f  %s%s%s%s\n", name.c_str(),
+                                tc, (long long)c.m, (long long)c.n, (long long)c.k, (long long)nb, g->p(), g->q(), es,
                                 r.time, gf, status.c_str(), (r.note.empty() || r.skipped) ? "" : "  ",
-                                r.skipped ? "" : r.note.c_str());
+                                r.skipped ? "" : r.note.c_str(), prec.c_str());
                     std::fflush(stdout);
                 }
                 if (P.timer_level >= 2) {
@@ -2012,6 +2024,7 @@ void usage() {
         "       [--timer-level 1|2] [--itermax N] [--fallback y|n] [--pivot-threshold X]\n"
         "       [--uplo l|u] [--trans n|t|c] [--side l|r] [--diag n|u] [--cond C] [--ib IB]\n"
         "       [--nonuniform-nb y|n] [--go c|r] [--do r|c]\n"
+        "       [--gemm-precision native|bf16|bf16x3|bf16x6]\n"
         "routines:");
     for (auto const& kv : routines<double>()) std::printf(" %s", kv.first.c_str());
     std::printf("\n");
@@ -2067,6 +2080,11 @@ int main(int argc, char** argv) {
         else if (a == "--nonuniform-nb") P.nonuniform = val()[0] == 'y';
         else if (a == "--go") P.order = char(std::tolower(val()[0])) == 'r' ? GridOrder::Row : GridOrder::Col;
         else if (a == "--do") P.dev_order = char(std::tolower(val()[0]));
+        else if (a == "--gemm-precision") {
+            try { P.gemm_precision = str2gemm_precision(val()); }
+            catch (std::exception const& e) { std::fprintf(stderr, "%s\n", e.what()); usage(); return 2; }
+            P.has_gemm_precision = true;
+        }
         else if (!a.empty() && a[0] != '-') rlist = rlist.empty() ? a : rlist + "," + a;
         else { usage(); return 2; }
     }

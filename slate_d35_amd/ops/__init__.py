@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -55,6 +55,25 @@ def gemm(opA: str, opB: str, alpha, A, B, beta, C):
     pc, mc, nc, ldc = _cm(C)
     k = na if opA == "N" else ma
     fn(opA, opB, mc, nc, k, alpha, pa, lda, pb, ldb, beta, pc, ldc)
+
+
+def gemm_lowprec(mode: str, opA: str, opB: str, alpha, A, B, beta, C, uplo: str = "G"):
+    """gemm on float32 tensors by the split-operand bf16 MFMA kernel: mode
+    "bf16", "bf16x3" or "bf16x6" (1, 3 or 6 bf16 plane products per K-step,
+    fp32 accumulation).  uplo "L" / "U" updates only that triangle of a
+    square C.  Conventions of gemm."""
+    import torch
+    assert A.dtype == B.dtype == C.dtype == torch.float32, "float32 tensors expected"
+    pa, ma, na, lda = _cm(A)
+    pb, mb, nb, ldb = _cm(B)
+    pc, mc, nc, ldc = _cm(C)
+    k = na if opA == "N" else ma
+    _slate.lb_gemm_lowprec(mode, uplo, opA, opB, mc, nc, k, float(alpha), pa, lda, pb, ldb, float(beta), pc, ldc)
+
+
+def lowprec_gemm_calls() -> int:
+    """Launches of the split-operand bf16 kernel in this process so far."""
+    return _slate.lowprec_gemm_calls()
 
 
 def gemm_async(queue: int, opA: str, opB: str, alpha, A, B, beta, C):

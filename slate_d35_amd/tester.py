@@ -47,9 +47,14 @@ def parse_dims(spec):
     return out
 
 
+# routines that take --gemm-precision (Option::GemmPrecision)
+TAKES_GEMM_PRECISION = {"gemm", "getrf", "getrf_tntpiv", "getrf_nopiv", "potrf", "gesv_mixed", "gesv_mixed_gmres",
+                        "posv_mixed", "posv_mixed_gmres"}
+
+
 class Ctx:
-    def __init__(self, a, dt, n, nb):
-        self.a, self.dt, self.nb = a, dt, nb
+    def __init__(self, a, dt, n, nb, name=""):
+        self.a, self.dt, self.nb, self.name = a, dt, nb, name
         if isinstance(n, tuple):
             self.m, self.n = n[0], n[1]
             self.k = n[2] if len(n) > 2 else n[1]
@@ -68,8 +73,15 @@ class Ctx:
             full = full + m * np.eye(m, n, dtype=self.dt)
         return full.astype(self.dt), core.from_numpy(full.astype(self.dt), nb=self.nb, target=self.target)
 
+    def gemm_precision(self):
+        gp = getattr(self.a, "gemm_precision", None)
+        return gp if gp and self.name in TAKES_GEMM_PRECISION else None
+
     def opts(self):
-        return dict(target=self.target, lookahead=self.a.lookahead)
+        o = dict(target=self.target, lookahead=self.a.lookahead)
+        if self.gemm_precision():
+            o["gemm_precision"] = self.gemm_precision()
+        return o
 
 
 def backward(a, x, b):
@@ -346,6 +358,8 @@ def main(argv=None):
     ap.add_argument("--check", default="y")
     ap.add_argument("--tol", type=float, default=50.0)
     ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--gemm-precision", default=None, choices=["native", "bf16", "bf16x3", "bf16x6"],
+                    help="arithmetic of the fp32 trailing updates of gemm, getrf*, potrf and the mixed solvers")
     a = ap.parse_args(argv)
     a.check = a.check.lower().startswith("y")
     world = parallel.world_size()
@@ -370,7 +384,7 @@ def main(argv=None):
             for dim in parse_dims(a.dim):
                 for nb in parse_dims(a.nb):
                     for _ in range(a.repeat):
-                        c = Ctx(a, dt, dim, nb)
+                        c = Ctx(a, dt, dim, nb, name)
                         try:
                             t, err = fn(c)
                             ok = err is None or err <= a.tol * eps(dt)
@@ -383,7 +397,9 @@ def main(argv=None):
                         if rank == 0:
                             es = "NA" if err is None else f"{err:.2e}"
                             print(f"{name:18s} {tch:4s} {c.m:6d} {c.n:6d} {c.k:6d} {nb:5d} {p:2d} {q:2d} "
-                                  f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}", flush=True)
+                                  f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}"
+                                  + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else ""),
+                                  flush=True)
     if rank == 0:
         print(f"# {nfail} failed" if nfail else "# all tests passed")
     return 1 if nfail else 0
