@@ -30,8 +30,12 @@ enum {
     slate_Option_EscalateGmres = 12, slate_Option_GemmPrecision = 13,
     slate_Option_MethodCholQR = 60, slate_Option_MethodEig = 61, slate_Option_MethodGels = 62,
     slate_Option_MethodGemm = 63, slate_Option_MethodHemm = 64, slate_Option_MethodLU = 65,
-    slate_Option_MethodTrsm = 66
+    slate_Option_MethodTrsm = 66, slate_Option_MethodSVD = 67
 };
+
+/* ivalue of slate_Option_MethodSVD (slate::MethodSVD): bidiagonal stage of
+ * slate_svd* with vectors, QR iteration (default) or divide and conquer */
+enum { slate_MethodSVD_QR = 81, slate_MethodSVD_DC = 68 };
 
 /* ivalue of slate_Option_GemmPrecision (slate::GemmPrecision): arithmetic of
  * the fp32 trailing updates of gemm, the LU family and Cholesky; the mixed

@@ -43,6 +43,10 @@ enum class LayoutConvert : char { ColMajor = 'C', RowMajor = 'R', None = 'N' };
 /// Eigenvalue method (enums.hh MethodEig).
 enum class MethodEig : char { QR = 'Q', DC = 'D' };
 
+/// Bidiagonal SVD method of svd with vectors: implicit-shift QR iteration
+/// (bdsqr, default) or divide and conquer (bdsdc).  Not in the reference.
+enum class MethodSVD : char { QR = 'Q', DC = 'D' };
+
 /// Arithmetic of the large device fp32 products (trailing updates) of a
 /// routine: the fp32 MFMA kernels, or the split-operand bf16 MFMA kernel with
 /// 1, 3 or 6 plane products per K-step (gemm_bf16s.hip).  Not in the reference.
@@ -85,6 +89,8 @@ enum class Option : char {
     MethodHemm,
     MethodLU,
     MethodTrsm,
+    /// MethodSVD of svd / gesvd with vectors.  Default QR.  Not in the reference.
+    MethodSVD,
 };
 
 const int HostNum    = -1;

@@ -64,16 +64,17 @@ SLATE_SECULAR_FN Sums<R> sums(int64_t k, int64_t j, const R* d, const R* z, int6
     return s;
 }
 
-/// Root j (0-based) of the secular equation; *org receives the origin pole.
-/// sum_fn(o, t) -> Sums<R> evaluates psi / phi and their derivatives (the
-/// serial `sums` here; the device kernel passes a wave-parallel one, every
-/// lane then runs the same iteration on the same reduced values).
-template <typename R, typename SumFn>
-SLATE_SECULAR_FN R root_with(int64_t k, int64_t j, R rho, const R* d, R znorm2, int64_t* org, SumFn&& sum_fn) {
+/// The iteration itself, on poles known only through their differences:
+/// diff(i, o) = pole_i - pole_o.  root_with passes d[i] - d[o]; the bidiagonal
+/// divide and conquer (kernels/bdsdc.hip) has poles d_i^2 and passes the
+/// product (d_i - d_o)(d_i + d_o), so no difference of squared values is ever
+/// formed; its sum_fn builds delta_i from the same product.
+template <typename R, typename DiffFn, typename SumFn>
+SLATE_SECULAR_FN R root_core(int64_t k, int64_t j, R rho, R znorm2, int64_t* org, DiffFn&& diff, SumFn&& sum_fn) {
     const R eps = std::numeric_limits<R>::epsilon();
     const R rhoinv = R(1) / rho;
     const bool last = j + 1 >= k;
-    const R gap = last ? rho * znorm2 : d[j + 1] - d[j];
+    const R gap = last ? rho * znorm2 : diff(j + 1, j);
     int64_t o = j;
     R a = 0, b = gap, t = gap / 2;
     if (!last) {
@@ -83,7 +84,7 @@ SLATE_SECULAR_FN R root_with(int64_t k, int64_t j, R rho, const R* d, R znorm2, 
         if (rhoinv + s.psi + s.phi < R(0)) { o = j + 1; a = -gap / 2; b = 0; t = -gap / 4; }
         else { b = gap / 2; t = gap / 4; }
     }
-    const R dj0 = d[j] - d[o], dj1 = last ? R(0) : d[j + 1] - d[o];
+    const R dj0 = diff(j, o), dj1 = last ? R(0) : diff(j + 1, o);
     for (int it = 0; it < 200; ++it) {
         const Sums<R> s = sum_fn(o, t);
         const R w = rhoinv + s.psi + s.phi;
@@ -119,9 +120,27 @@ SLATE_SECULAR_FN R root_with(int64_t k, int64_t j, R rho, const R* d, R znorm2, 
     return t;
 }
 
+/// Root j (0-based) of the secular equation; *org receives the origin pole.
+/// sum_fn(o, t) -> Sums<R> evaluates psi / phi and their derivatives (the
+/// serial `sums` here; the device kernel passes a wave-parallel one, every
+/// lane then runs the same iteration on the same reduced values).
+template <typename R, typename SumFn>
+SLATE_SECULAR_FN R root_with(int64_t k, int64_t j, R rho, const R* d, R znorm2, int64_t* org, SumFn&& sum_fn) {
+    return root_core<R>(k, j, rho, znorm2, org, [d](int64_t i, int64_t o) { return d[i] - d[o]; }, sum_fn);
+}
+
 template <typename R>
 SLATE_SECULAR_FN R root(int64_t k, int64_t j, R rho, const R* d, const R* z, R znorm2, int64_t* org) {
     return root_with<R>(k, j, rho, d, znorm2, org, [&](int64_t o, R t) { return sums(k, j, d, z, o, t); });
+}
+
+/// Poles d_i^2 (singular values): the converged shift t = sigma^2 - d_o^2 as
+/// tau = sigma - d_o = t / (sigma + d_o), free of cancellation (the origin is
+/// the nearer pole, so d_o^2 + t >= d_o^2 / 2).
+template <typename R>
+SLATE_SECULAR_FN R sqrt_shift(R d_o, R t) {
+    const R den = std::sqrt(std::fmax(d_o * d_o + t, R(0))) + d_o;
+    return den > R(0) ? t / den : R(0);
 }
 
 }  // namespace secular

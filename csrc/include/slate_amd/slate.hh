@@ -351,6 +351,23 @@ void stedc_merge(Matrix<R>& Q, Matrix<R>& U, Matrix<R>& Qout, Options const& opt
 template <typename T>
 void bdsqr(Job jobu, Job jobvt, std::vector<real_type<T>>& D, std::vector<real_type<T>>& E, Matrix<T>& U,
            Matrix<T>& VT, Options const& opts = {});
+/// Bidiagonal SVD by divide and conquer (src/bdsdc.cc), the contract of bdsqr:
+/// D descending singular values, U := U Ub, VT := Vb^T VT, E destroyed.  Every
+/// process runs the whole divide and conquer on local arrays (about 4 n^2
+/// reals, device memory on the device target).  Accuracy is absolute
+/// (eps ||B||).  Without vectors it is the values-only QR iteration.
+template <typename T>
+void bdsdc(Job jobu, Job jobvt, std::vector<real_type<T>>& D, std::vector<real_type<T>>& E, Matrix<T>& U,
+           Matrix<T>& VT, Options const& opts = {});
+/// Counters of the last divide and conquer of this process (bdsdc, or svd
+/// with MethodSVD::DC): merges, merged and deflated columns in all and per
+/// tree level (0 = root), launches of the three device kernels.
+struct BdsdcStats {
+    int64_t merges = 0, columns = 0, deflated = 0;
+    int64_t launches_secular = 0, launches_zhat = 0, launches_matrix = 0;
+    std::vector<int64_t> level_columns, level_deflated;
+};
+BdsdcStats bdsdc_stats();
 
 //------------------------------------------------------------------------------
 // Real-symmetric aliases (real types only) and compatibility names.

@@ -51,6 +51,7 @@ public:
     OptionValue(bool b) : i_(b), d_(b) {}
     OptionValue(Target t) : i_(int64_t(t)), d_(0) {}
     OptionValue(MethodEig m) : i_(int64_t(m)), d_(0) {}
+    OptionValue(MethodSVD m) : i_(int64_t(m)), d_(0) {}
     OptionValue(GemmPrecision g) : i_(int64_t(g)), d_(0) {}
     int64_t i_;
     double d_;

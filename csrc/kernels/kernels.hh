@@ -123,6 +123,39 @@ template <typename T>
 void merge_matrix(StedcMerge const& m, int64_t c_first, int64_t ncols, T* M, int64_t ldm, double* scratch,
                   hipStream_t s);
 
+// ---- bidiagonal divide and conquer (bdsdc.hip)
+/// roots of 1 + sum z_i^2 / ((d_i - sigma)(d_i + sigma)) (dd ascending, dd[0] = 0): sigma_j = dd[org[j]] + tau[j]
+void bdsdc_secular_roots(int64_t k, const double* dd, const double* zz, double znorm2, int64_t* org, double* tau,
+                         hipStream_t s);
+/// z recomputed from the roots (Loewner / Gu-Eisenstat)
+void bdsdc_zhat(int64_t k, const double* dd, const double* zz, const int64_t* org, const double* tau, double* zh,
+                hipStream_t s);
+/// one merge's device vectors (see bdsdc.hip); n sorted-basis entries, k of them not deflated, row nl of the
+/// block is the removed row / q1, row n (right side, sqre = 1) is q2, (qc, qs) the (q1, q2) rotation
+struct BdsdcMerge {
+    int64_t n = 0, k = 0, nl = 0, sqre = 0, nrot_u = 0, nrot_v = 0;
+    double qc = 1, qs = 0;
+    const double *dd = nullptr, *zh = nullptr, *tau = nullptr;
+    const int64_t *org = nullptr, *act = nullptr, *defl = nullptr, *ord = nullptr, *inv_perm = nullptr;
+    const int64_t *rot_ab_u = nullptr, *rot_ab_v = nullptr;
+    const double *rot_cs_u = nullptr, *rot_cs_v = nullptr;
+};
+/// columns [c_first, c_first + ncols) of MU (vside false, n x n) or MV (n + sqre square) into M; scratch:
+/// ncols * n reals
+template <typename T>
+void bdsdc_merge_matrices(BdsdcMerge const& m, bool vside, int64_t c_first, int64_t ncols, T* M, int64_t ldm,
+                          double* scratch, hipStream_t s);
+/// block-cyclic local part (lrows x lcols) of op(src) with an optional row phase:
+/// dst(lr, lc) = phase[gi] * op(src)(gi, gj), gi = ((lr / mb) p + rrel) mb + lr % mb, gj likewise
+struct BdsdcPlace {
+    int64_t m = 0, n = 0;           // op(src) is m x n
+    int64_t lrows = 0, lcols = 0, mb = 1, p = 1, rrel = 0, nb = 1, q = 1, crel = 0;
+    int trans = 0;
+};
+template <typename T>
+void bdsdc_place(BdsdcPlace const& p, const rt<T>* src, int64_t lds, const T* phase, T* dst, int64_t ldd,
+                 hipStream_t s);
+
 // ---- eigensolver back-transform (eig.hip)
 /// G (k x k Gram V^H V) -> T^{-1} = striu(G) + diag(1 / tau) in place.
 /// Stage-2 back-transform (hb2st_apply.hip), fp64.  ng groups of 64

@@ -171,6 +171,13 @@ Options to_options(py::dict d) {
         else if (k == "method_cholqr") o[Option::MethodCholQR] = meth(v, MethodCholQR::str2method);
         else if (k == "method_hemm") o[Option::MethodHemm] = meth(v, MethodHemm::str2method);
         else if (k == "method_eig") o[Option::MethodEig] = OptionValue(int64_t(v.cast<std::string>()[0]));
+        else if (k == "method_svd") {
+            std::string mname = v.cast<std::string>();
+            for (auto& ch : mname) ch = char(std::tolower((unsigned char)ch));
+            if (mname == "qr") o[Option::MethodSVD] = MethodSVD::QR;
+            else if (mname == "dc") o[Option::MethodSVD] = MethodSVD::DC;
+            else throw Exception("method_svd: \"qr\" or \"dc\", not " + mname);
+        }
         else if (k == "print_verbose") o[Option::PrintVerbose] = v.cast<int64_t>();
         else if (k == "print_edge_items") o[Option::PrintEdgeItems] = v.cast<int64_t>();
         else if (k == "print_width") o[Option::PrintWidth] = v.cast<int64_t>();
@@ -417,6 +424,7 @@ PYBIND11_MODULE(_slate, m) {
     py::enum_<GridOrder>(m, "GridOrder").value("Col", GridOrder::Col).value("Row", GridOrder::Row);
     py::enum_<Equed>(m, "Equed").value("None_", Equed::None).value("Row", Equed::Row).value("Col", Equed::Col)
         .value("Both", Equed::Both);
+    py::enum_<MethodSVD>(m, "MethodSVD").value("QR", MethodSVD::QR).value("DC", MethodSVD::DC);
     py::enum_<Job>(m, "Job").value("NoVec", Job::NoVec).value("Vec", Job::Vec);
 
     py::class_<Comm, std::shared_ptr<Comm>>(m, "Comm")
@@ -546,6 +554,19 @@ PYBIND11_MODULE(_slate, m) {
         slate_hip_call(hipStreamSynchronize(c.stream));
     });
     m.def("lowprec_gemm_calls", &lb::lowprec_gemm_calls);
+    m.def("bdsdc_stats", []() {
+        const BdsdcStats st = bdsdc_stats();
+        py::dict r;
+        r["merges"] = st.merges;
+        r["columns"] = st.columns;
+        r["deflated"] = st.deflated;
+        r["launches_secular"] = st.launches_secular;
+        r["launches_zhat"] = st.launches_zhat;
+        r["launches_matrix"] = st.launches_matrix;
+        r["level_columns"] = st.level_columns;
+        r["level_deflated"] = st.level_deflated;
+        return r;
+    });
     m.def("queue_sync", [](int q) { slate_hip_call(hipStreamSynchronize(device::queue(q))); },
           py::call_guard<py::gil_scoped_release>());
     m.def("release_cache", &device::release_cache);
@@ -585,6 +606,17 @@ PYBIND11_MODULE(_slate, m) {
         VD U(n * n), VT(n * n);
         for (int64_t i = 0; i < n; ++i) { U[i + i * n] = 1; VT[i + i * n] = 1; }
         slate::host::bdsqr<double, double>(n, d.data(), e.data(), U.data(), n, n, VT.data(), n, n);
+        return py::make_tuple(d, mat(U, n, n), mat(VT, n, n)); });
+    m.def("bdsdc", [=](VD d, VD e) {
+        int64_t n = d.size();
+        VD U(n * n), VT(n * n);
+        for (int64_t i = 0; i < n; ++i) { U[i + i * n] = 1; VT[i + i * n] = 1; }
+        e.resize(std::max<int64_t>(n - 1, 0));
+        if (n > 0) {
+            py::gil_scoped_release r;
+            auto Um = Matrix<double>::fromLAPACK(n, n, U.data(), n, n), Vm = Matrix<double>::fromLAPACK(n, n, VT.data(), n, n);
+            slate::bdsdc(Job::Vec, Job::Vec, d, e, Um, Vm, {{Option::Target, Target::HostTask}});
+        }
         return py::make_tuple(d, mat(U, n, n), mat(VT, n, n)); });
     // bdsqr's host loop alone (rotations generated and handed to a sink that
     // only keeps them, as the device sink's batching does): its cost bounds

@@ -331,6 +331,11 @@ void bind_drivers(py::module_& m, std::string const& s) {
         Options op = to_options(o); Matrix<T> U = opt_mat(u), VT = opt_mat(vt);
         { py::gil_scoped_release r; bdsqr(ju, jv, D, E, U, VT, op); }
         return D; });
+    DEF("bdsdc_mat", [=](Job ju, Job jv, std::vector<R> D, std::vector<R> E, py::object u, py::object vt,
+                         py::dict o) {
+        Options op = to_options(o); Matrix<T> U = opt_mat(u), VT = opt_mat(vt);
+        { py::gil_scoped_release r; bdsdc(ju, jv, D, E, U, VT, op); }
+        return D; });
     DEF("gels_cholqr", [](Matrix<T>& A, Matrix<T>& Rm, Matrix<T>& BX, py::dict o) {
         Options op = to_options(o); py::gil_scoped_release r; gels_cholqr(A, Rm, BX, op); });
     DEF("gels_qr", [](Matrix<T>& A, Matrix<T>& BX, py::dict o) {

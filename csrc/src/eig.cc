@@ -1138,13 +1138,26 @@ void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Ma
     Matrix<T> U2(n, n, kd, n, gr), V2(n, n, kd, n, gr);
     U2.insertLocalTiles(target);
     V2.insertLocalTiles(target);
-    {
+    const int64_t msvd = get_option<int64_t>(opts, Option::MethodSVD, int64_t(MethodSVD::QR));
+    slate_error_if_msg(msvd != int64_t(MethodSVD::QR) && msvd != int64_t(MethodSVD::DC),
+                       "svd: Option::MethodSVD is neither MethodSVD::QR nor MethodSVD::DC");
+    if (msvd == int64_t(MethodSVD::DC)) {
+        // divide and conquer, replicated on local arrays (bdsdc.cc):
+        // U2 = diag(pu) U_B, V2 = diag(conj pv) V_B, every rank its own rows
+        trace::Block t2("bdsdc");
+        std::vector<T> cpv(n);
+        for (int64_t i = 0; i < n; ++i) cpv[i] = slate::conj(pv[i]);
+        Work<R> UB(target, size_t(n) * n), VB(target, size_t(n) * n);
+        bdsdc_local<R>(c, d, e, UB.data(), VB.data(), n);
+        bdsdc_place<T>(c, U2, UB.data(), n, false, pu);
+        bdsdc_place<T>(c, V2, VB.data(), n, false, cpv);
+    } else {
         std::vector<T> cpv(n);
         for (int64_t i = 0; i < n; ++i) cpv[i] = slate::conj(pv[i]);
         set_diag_rows(U2, pu, target);
         set_diag_rows(V2, cpv, target);
     }
-    {
+    if (msvd != int64_t(MethodSVD::DC)) {
         trace::Block t2("bdsqr");
         LocalBlock<T> lu = U2.local(loc_of(target), true), lv = V2.local(loc_of(target), true);
         RowRotSink<T> sink(c, n);

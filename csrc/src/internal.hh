@@ -295,6 +295,17 @@ void stedc_dist(std::vector<R>& d, std::vector<R> const& e, Matrix<R>& Q, Option
 template <typename T>
 int64_t steqr2_dist(std::vector<real_type<T>>& d, std::vector<real_type<T>>& e, Matrix<T>& Z, Options const& opts);
 
+/// Bidiagonal divide and conquer on local column-major arrays of c's memory
+/// (bdsdc.cc): B(D, E) = UB diag(D) VB^T, UB / VB n x n with leading
+/// dimension ld, D descending.  Replicated: every caller computes all of it.
+template <typename R>
+void bdsdc_local(lb::Ctx const& c, std::vector<R>& D, std::vector<R> const& E, R* UB, R* VB, int64_t ld);
+/// A's local entries := phase[i] * op(src)(i, j) (src real, local, op(src) of
+/// A's size; phase may be empty); A a whole NoTrans matrix.
+template <typename T>
+void bdsdc_place(lb::Ctx const& c, Matrix<T>& A, real_type<T> const* src, int64_t lds, bool trans,
+                 std::vector<T> const& phase);
+
 /// Apply LU pivots to the rows of B (forward: P B; backward: P^T B).
 template <typename T>
 void apply_pivots(Pivots const& pivots, BaseMatrix<T> const& A, Matrix<T>& B, Target target, bool forward);

@@ -58,6 +58,9 @@ struct Params {
     // the getrf family, potrf and the mixed solvers (unset: not passed)
     bool has_gemm_precision = false;
     GemmPrecision gemm_precision = GemmPrecision::Native;
+    // --method-svd qr|dc: Option::MethodSVD of svd
+    bool has_method_svd = false;
+    MethodSVD method_svd = MethodSVD::QR;
     // operand shape flags of the BLAS-3 / triangular routines (reference
     // --uplo --trans --side --diag)
     Uplo uplo = Uplo::Lower;
@@ -1442,7 +1445,7 @@ void test_tridiag(int64_t n, std::vector<R>& d, std::vector<R>& e) {
 }
 
 template <typename T>
-Result r_bdsqr(Case<T>& c) {   // B = U diag(s) VT for an upper bidiagonal B
+Result r_bdsqr(Case<T>& c, bool dc = false) {   // B = U diag(s) VT for an upper bidiagonal B; dc: bdsdc
     using R = R_<T>;
     const int64_t n = c.n;
     std::vector<R> d, e;
@@ -1453,7 +1456,10 @@ Result r_bdsqr(Case<T>& c) {   // B = U diag(s) VT for an upper bidiagonal B
     set(T(0), T(1), U, c.opts);
     set(T(0), T(1), VT, c.opts);
     Result r;
-    r.time = c.timed([&] { bdsqr(Job::Vec, Job::Vec, d, e, U, VT, c.opts); });
+    r.time = c.timed([&] {
+        if (dc) bdsdc(Job::Vec, Job::Vec, d, e, U, VT, c.opts);
+        else bdsqr(Job::Vec, Job::Vec, d, e, U, VT, c.opts);
+    });
     r.flops = 12.0 * double(n) * n * n;
     if (c.P.check) {
         auto Bm = c.zeros(n, n);
@@ -1911,7 +1917,8 @@ std::map<std::string, Fn<T>> routines() {
         {"ge2tb", r_ge2tb<T>},
         {"tb2bd", [](Case<T>& c) { return r_tb2bd<T>(c, 0); }},
         {"unmbr_tb2bd", [](Case<T>& c) { return r_tb2bd<T>(c, 1); }},
-        {"bdsqr", r_bdsqr<T>},
+        {"bdsqr", [](Case<T>& c) { return r_bdsqr<T>(c); }},
+        {"bdsdc", [](Case<T>& c) { return r_bdsqr<T>(c, true); }},
         {"stedc", r_stedc<T>},
         {"hegst", r_hegst<T>},
         {"getrs_nopiv", [](Case<T>& c) { return r_getrs_v<T>(c, 0); }},
@@ -1973,6 +1980,8 @@ int run_type(Params const& P, char tc, std::string const& name) {
                     "posv_mixed", "posv_mixed_gmres"};
                 const bool with_precision = P.has_gemm_precision && takes_precision.count(name) > 0;
                 if (with_precision) c.opts[Option::GemmPrecision] = P.gemm_precision;
+                const bool with_method_svd = P.has_method_svd && name == "svd";
+                if (with_method_svd) c.opts[Option::MethodSVD] = P.method_svd;
                 Result r;
                 std::string status;
                 try {
@@ -1993,7 +2002,9 @@ int run_type(Params const& P, char tc, std::string const& name) {
                     else std::snprintf(es, sizeof(es), "%10s", "NA");
                     double gf = (r.time > 0 && r.flops > 0) ? r.flops / r.time / 1e9 : NAN;
                     const std::string prec =
-                        with_precision ? std::string("  gemm_precision=") + to_string(P.gemm_precision) : "";
+                        (with_precision ? std::string("  gemm_precision=") + to_string(P.gemm_precision) : "") +
+                        (with_method_svd ? std::string("  method_svd=") + (P.method_svd == MethodSVD::DC ? "dc" : "qr")
+                                         : "");
                     std::printf("%-16s %-4c %7lld %7lld %7lld %5lld %2d %2d %s %10.4f %11.2f  %s%s%s%s\n", name.c_str(),
                                 tc, (long long)c.m, (long long)c.n, (long long)c.k, (long long)nb, g->p(), g->q(), es,
                                 r.time, gf, status.c_str(), (r.note.empty() || r.skipped) ? "" : "  ",
@@ -2024,7 +2035,7 @@ void usage() {
         "       [--timer-level 1|2] [--itermax N] [--fallback y|n] [--pivot-threshold X]\n"
         "       [--uplo l|u] [--trans n|t|c] [--side l|r] [--diag n|u] [--cond C] [--ib IB]\n"
         "       [--nonuniform-nb y|n] [--go c|r] [--do r|c]\n"
-        "       [--gemm-precision native|bf16|bf16x3|bf16x6]\n"
+        "       [--gemm-precision native|bf16|bf16x3|bf16x6] [--method-svd qr|dc]\n"
         "routines:");
     for (auto const& kv : routines<double>()) std::printf(" %s", kv.first.c_str());
     std::printf("\n");
@@ -2084,6 +2095,13 @@ int main(int argc, char** argv) {
             try { P.gemm_precision = str2gemm_precision(val()); }
             catch (std::exception const& e) { std::fprintf(stderr, "%s\n", e.what()); usage(); return 2; }
             P.has_gemm_precision = true;
+        }
+        else if (a == "--method-svd") {
+            std::string v = val();
+            for (auto& ch : v) ch = char(std::tolower((unsigned char)ch));
+            if (v != "qr" && v != "dc") { std::fprintf(stderr, "--method-svd: qr or dc\n"); usage(); return 2; }
+            P.method_svd = v == "dc" ? MethodSVD::DC : MethodSVD::QR;
+            P.has_method_svd = true;
         }
         else if (!a.empty() && a[0] != '-') rlist = rlist.empty() ? a : rlist + "," + a;
         else { usage(); return 2; }

@@ -14,6 +14,7 @@ Target = _slate.Target
 Op = _slate.Op
 Uplo = _slate.Uplo
 Job = _slate.Job
+MethodSVD = _slate.MethodSVD
 Diag = _slate.Diag
 Side = _slate.Side
 Norm = _slate.Norm

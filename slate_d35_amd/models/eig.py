@@ -5,7 +5,8 @@ from ._wrap import call
 
 __all__ = ["heev", "hegv", "hegst", "svd", "svd_vals", "gesvd", "eig", "eig_vals", "he2hb", "hb2st", "sterf",
            "steqr", "stedc", "ge2tb", "tb2bd", "bdsqr", "syev", "sygv", "hb2st_band", "unmtr_hb2st",
-           "unmtr_he2hb", "tb2bd_band", "unmbr_tb2bd", "unmbr_ge2tb", "steqr2", "stedc_matrix", "bdsqr_matrix"]
+           "unmtr_he2hb", "tb2bd_band", "unmbr_tb2bd", "unmbr_ge2tb", "steqr2", "stedc_matrix", "bdsqr_matrix",
+           "bdsdc", "bdsdc_matrix"]
 
 
 def heev(A, Z=None, target=None, **kw):
@@ -28,7 +29,8 @@ def hegst(itype, A, B, target=None, **kw):
 
 def svd(A, U=None, VT=None, target=None, **kw):
     """Singular values (descending numpy array); thin U (m x k) and VT
-    (k x n), k = min(m, n), filled when given."""
+    (k x n), k = min(m, n), filled when given.  method_svd="qr" (bidiagonal
+    QR iteration, default) or "dc" (divide and conquer, bdsdc)."""
     import numpy as np
     return np.asarray(call("svd", A, A, U, VT, target=target, **kw))
 
@@ -147,3 +149,17 @@ def bdsqr_matrix(jobu, jobvt, d, e, U=None, VT=None, target=None, **kw):
     import numpy as np
     key = U if U is not None else VT
     return np.asarray(call("bdsqr_mat", key, jobu, jobvt, list(d), list(e), U, VT, target=target, **kw))
+
+
+def bdsdc(d, e, **kw):
+    """Bidiagonal divide and conquer on the host: (sv, u, vt) like bdsqr."""
+    from .. import _slate
+    return _slate.bdsdc(list(d), list(e))
+
+
+def bdsdc_matrix(jobu, jobvt, d, e, U=None, VT=None, target=None, **kw):
+    """Bidiagonal divide and conquer on distributed matrices, the contract of
+    bdsqr_matrix: U := U U_B, VT := V_B^T VT, singular values returned."""
+    import numpy as np
+    key = U if U is not None else VT
+    return np.asarray(call("bdsdc_mat", key, jobu, jobvt, list(d), list(e), U, VT, target=target, **kw))

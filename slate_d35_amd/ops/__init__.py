@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -74,6 +74,14 @@ def gemm_lowprec(mode: str, opA: str, opB: str, alpha, A, B, beta, C, uplo: str 
 def lowprec_gemm_calls() -> int:
     """Launches of the split-operand bf16 kernel in this process so far."""
     return _slate.lowprec_gemm_calls()
+
+
+def bdsdc_stats() -> dict:
+    """Counters of the last bidiagonal divide and conquer of this process
+    (bdsdc, or svd with method_svd="dc"): merges, merged and deflated columns
+    (in all and per tree level, root first) and the launches of the three
+    device kernels (zero on the host target)."""
+    return _slate.bdsdc_stats()
 
 
 def gemm_async(queue: int, opA: str, opB: str, alpha, A, B, beta, C):

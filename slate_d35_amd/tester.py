@@ -77,10 +77,16 @@ class Ctx:
         gp = getattr(self.a, "gemm_precision", None)
         return gp if gp and self.name in TAKES_GEMM_PRECISION else None
 
+    def method_svd(self):
+        ms = getattr(self.a, "method_svd", None)
+        return ms if ms and self.name == "svd" else None
+
     def opts(self):
         o = dict(target=self.target, lookahead=self.a.lookahead)
         if self.gemm_precision():
             o["gemm_precision"] = self.gemm_precision()
+        if self.method_svd():
+            o["method_svd"] = self.method_svd()
         return o
 
 
@@ -360,6 +366,8 @@ def main(argv=None):
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--gemm-precision", default=None, choices=["native", "bf16", "bf16x3", "bf16x6"],
                     help="arithmetic of the fp32 trailing updates of gemm, getrf*, potrf and the mixed solvers")
+    ap.add_argument("--method-svd", default=None, choices=["qr", "dc"],
+                    help="bidiagonal stage of svd: QR iteration (default) or divide and conquer")
     a = ap.parse_args(argv)
     a.check = a.check.lower().startswith("y")
     world = parallel.world_size()
@@ -398,7 +406,8 @@ def main(argv=None):
                             es = "NA" if err is None else f"{err:.2e}"
                             print(f"{name:18s} {tch:4s} {c.m:6d} {c.n:6d} {c.k:6d} {nb:5d} {p:2d} {q:2d} "
                                   f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}"
-                                  + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else ""),
+                                  + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else "")
+                                  + (f"  method_svd={c.method_svd()}" if c.method_svd() else ""),
                                   flush=True)
     if rank == 0:
         print(f"# {nfail} failed" if nfail else "# all tests passed")
