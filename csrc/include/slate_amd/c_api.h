@@ -30,8 +30,14 @@ enum {
     slate_Option_EscalateGmres = 12, slate_Option_GemmPrecision = 13,
     slate_Option_MethodCholQR = 60, slate_Option_MethodEig = 61, slate_Option_MethodGels = 62,
     slate_Option_MethodGemm = 63, slate_Option_MethodHemm = 64, slate_Option_MethodLU = 65,
-    slate_Option_MethodTrsm = 66, slate_Option_MethodSVD = 67
+    slate_Option_MethodTrsm = 66, slate_Option_MethodSVD = 67,
+    slate_Option_MethodHetrd = 68
 };
+
+/* ivalue of slate_Option_MethodHetrd (slate::MethodHetrd): tridiagonal
+ * reduction of slate_hermitian_eig*, two stages (default) or the one-stage
+ * hetrd (real types, one process) */
+enum { slate_MethodHetrd_TwoStage = 50, slate_MethodHetrd_OneStage = 49 };
 
 /* ivalue of slate_Option_MethodSVD (slate::MethodSVD): bidiagonal stage of
  * slate_svd* with vectors, QR iteration (default) or divide and conquer */

@@ -138,5 +138,12 @@ int64_t bdsqr_core(int64_t n, R* d, R* e, RotSink<R>* sink);
 template <typename R>
 int64_t steqr_core(int64_t n, R* d, R* e, RotSink<R>* sink);
 
+/// One-stage tridiagonal reduction of the lower triangle of a real symmetric
+/// A (LAPACK sytrd, panels of nb columns): A = Q T Q^T, T = tridiag(d, e) with
+/// signed e, Q = H_0 .. H_{n-2}, H_i = I - tau_i v_i v_i^T, v_i in A(i+1:n, i)
+/// with its unit entry stored.  The strict upper triangle is not read.
+template <typename R>
+void hetrd(int64_t n, R* A, int64_t lda, R* d, R* e, R* tau, int64_t nb);
+
 }  // namespace host
 }  // namespace slate

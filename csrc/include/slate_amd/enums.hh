@@ -47,6 +47,11 @@ enum class MethodEig : char { QR = 'Q', DC = 'D' };
 /// (bdsqr, default) or divide and conquer (bdsdc).  Not in the reference.
 enum class MethodSVD : char { QR = 'Q', DC = 'D' };
 
+/// Tridiagonal reduction of heev / syev / hegv / sygv: two stages (he2hb on
+/// the device, the bulge chase hb2st on the host; default) or the one-stage
+/// hetrd (sytrd panels, a symv per column on the device).  Not in the reference.
+enum class MethodHetrd : char { TwoStage = '2', OneStage = '1' };
+
 /// Arithmetic of the large device fp32 products (trailing updates) of a
 /// routine: the fp32 MFMA kernels, or the split-operand bf16 MFMA kernel with
 /// 1, 3 or 6 plane products per K-step (gemm_bf16s.hip).  Not in the reference.
@@ -91,6 +96,8 @@ enum class Option : char {
     MethodTrsm,
     /// MethodSVD of svd / gesvd with vectors.  Default QR.  Not in the reference.
     MethodSVD,
+    /// MethodHetrd of heev / syev / hegv / sygv.  Default TwoStage.  Not in the reference.
+    MethodHetrd,
 };
 
 const int HostNum    = -1;

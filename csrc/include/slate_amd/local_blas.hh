@@ -133,6 +133,12 @@ template <typename T>
 void trmm(Ctx const& c, Side side, Uplo uplo, Op op, Diag diag, int64_t m, int64_t n, T alpha,
           T const* A, int64_t lda, T* B, int64_t ldb);
 
+/// y = A x for the order-m real symmetric block of which only the lower
+/// triangle is stored: the strict upper triangle is never read.  Device: the
+/// split symv of kernels/hetrd.hip, no atomics, bitwise reproducible.
+template <typename R>
+void symv_lower(Ctx const& c, int64_t m, R const* A, int64_t lda, R const* x, R* y);
+
 // ---------------- LAPACK-style
 /// Cholesky of an n x n block; info (device int on Devices, host int on Host)
 /// receives info_offset + failing column if not already set.

@@ -369,6 +369,35 @@ struct BdsdcStats {
 };
 BdsdcStats bdsdc_stats();
 
+/// One-stage tridiagonal reduction (src/hetrd.cc; LAPACK sytrd): A = Q T Q^T
+/// with T = tridiag(D, E), E signed.  Real types, Uplo::Lower, a matrix of one
+/// process on one device or the host; anything else throws NotImplemented
+/// (Uplo::Upper: Exception).  The reflectors stay in A below the subdiagonal;
+/// T[0] holds the 64 x 64 block-reflector factor of every panel of 64 columns
+/// (panel p at column 64 p), T[1] the scalars tau.  The strict upper triangle
+/// of A is not read.
+template <typename T>
+void hetrd(HermitianMatrix<T>& A, std::vector<real_type<T>>& D, std::vector<real_type<T>>& E,
+           TriangularFactors<T>& T_, Options const& opts = {});
+/// C := op(Q) C (Side::Left) or C op(Q) (Side::Right), Q = H_0 H_1 .. H_{n-2}
+/// from hetrd(A, ..., T), panel by panel.
+template <typename T>
+void unmtr_hetrd(Side side, Op op, HermitianMatrix<T>& A, TriangularFactors<T>& T_, Matrix<T>& C,
+                 Options const& opts = {});
+/// Counters of the last one-stage reduction of this process (hetrd, or heev
+/// with MethodHetrd::OneStage): reduced columns, panels, launches of the four
+/// column kernels (zero on the host target) and host synchronisations inside
+/// the reduction.  With SLATE_HETRD_PROFILE=1 in the environment the device
+/// reduction also records events between its kernels and reports the device
+/// milliseconds of the symv launches, the other column kernels (panel), the
+/// syr2k updates and the T factors; zero otherwise.
+struct HetrdStats {
+    int64_t columns = 0, panels = 0, host_syncs = 0;
+    int64_t launches_column = 0, launches_larfg = 0, launches_symv = 0, launches_correct = 0;
+    double ms_symv = 0, ms_panel = 0, ms_syr2k = 0, ms_larft = 0;
+};
+HetrdStats hetrd_stats();
+
 //------------------------------------------------------------------------------
 // Real-symmetric aliases (real types only) and compatibility names.
 template <typename T>

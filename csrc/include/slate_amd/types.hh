@@ -52,6 +52,7 @@ public:
     OptionValue(Target t) : i_(int64_t(t)), d_(0) {}
     OptionValue(MethodEig m) : i_(int64_t(m)), d_(0) {}
     OptionValue(MethodSVD m) : i_(int64_t(m)), d_(0) {}
+    OptionValue(MethodHetrd m) : i_(int64_t(m)), d_(0) {}
     OptionValue(GemmPrecision g) : i_(int64_t(g)), d_(0) {}
     int64_t i_;
     double d_;

@@ -156,6 +156,40 @@ template <typename T>
 void bdsdc_place(BdsdcPlace const& p, const rt<T>* src, int64_t lds, const T* phase, T* dst, int64_t ldd,
                  hipStream_t s);
 
+// ---- one-stage tridiagonal reduction (hetrd.hip), float and double
+/// y = A x for the order-m symmetric block of which only the lower triangle is
+/// read (the strict upper triangle is never loaded).  No atomics: partials in
+/// work (symv_lower_workspace(m) elements), summed in a fixed order.
+template <typename R>
+void symv_lower(int64_t m, const R* A, int64_t lda, const R* x, R* y, R* work, hipStream_t s);
+int64_t symv_lower_workspace(int64_t m);
+/// row tiles per wave of the split of an order-m block, and its chunks per block column
+int symv_lower_tpw(int64_t m);
+int64_t symv_lower_chunks(int64_t m, int tpw);
+/// device vectors of a reduction of order n with panels of nb <= 64 columns
+template <typename R>
+struct HetrdWork {
+    R* W = nullptr;          // n x nb, leading dimension ldw
+    int64_t ldw = 0;
+    R *v = nullptr, *wraw = nullptr;         // n each: the current reflector, the uncorrected w
+    R *scal = nullptr;                       // 1: alpha of the current column
+    R *ssq = nullptr, *pdot = nullptr;       // ceil(n / 64) each: partial sums of squares, of w^T v
+    R *pvw = nullptr;                        // ceil(n / 256) x 128: partials of V^T v | W^T v
+    R *rowpart = nullptr, *colpart = nullptr;   // symv partials: (n / 16 + 2) n and (n / 64 + 2) n
+    R *d = nullptr, *e = nullptr, *tau = nullptr;   // n each
+};
+/// the four launches of column i of the panel that starts at j0 (see hetrd.hip); hetrd_column with
+/// update = false only finishes column i - 1 - j0 of W (end of a panel)
+template <typename R>
+void hetrd_column(int64_t n, int64_t i, int64_t j0, bool update, R* A, int64_t lda, HetrdWork<R> const& wk,
+                  hipStream_t s);
+template <typename R>
+void hetrd_larfg(int64_t n, int64_t i, R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s);
+template <typename R>
+void hetrd_symv(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s);
+template <typename R>
+void hetrd_correct(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s);
+
 // ---- eigensolver back-transform (eig.hip)
 /// G (k x k Gram V^H V) -> T^{-1} = striu(G) + diag(1 / tau) in place.
 /// Stage-2 back-transform (hb2st_apply.hip), fp64.  ng groups of 64

@@ -178,6 +178,13 @@ Options to_options(py::dict d) {
             else if (mname == "dc") o[Option::MethodSVD] = MethodSVD::DC;
             else throw Exception("method_svd: \"qr\" or \"dc\", not " + mname);
         }
+        else if (k == "method_hetrd") {
+            std::string mname = v.cast<std::string>();
+            for (auto& ch : mname) ch = char(std::tolower((unsigned char)ch));
+            if (mname == "two_stage") o[Option::MethodHetrd] = MethodHetrd::TwoStage;
+            else if (mname == "one_stage") o[Option::MethodHetrd] = MethodHetrd::OneStage;
+            else throw Exception("method_hetrd: \"two_stage\" or \"one_stage\", not " + mname);
+        }
         else if (k == "print_verbose") o[Option::PrintVerbose] = v.cast<int64_t>();
         else if (k == "print_edge_items") o[Option::PrintEdgeItems] = v.cast<int64_t>();
         else if (k == "print_width") o[Option::PrintWidth] = v.cast<int64_t>();
@@ -425,6 +432,8 @@ PYBIND11_MODULE(_slate, m) {
     py::enum_<Equed>(m, "Equed").value("None_", Equed::None).value("Row", Equed::Row).value("Col", Equed::Col)
         .value("Both", Equed::Both);
     py::enum_<MethodSVD>(m, "MethodSVD").value("QR", MethodSVD::QR).value("DC", MethodSVD::DC);
+    py::enum_<MethodHetrd>(m, "MethodHetrd").value("TwoStage", MethodHetrd::TwoStage)
+        .value("OneStage", MethodHetrd::OneStage);
     py::enum_<Job>(m, "Job").value("NoVec", Job::NoVec).value("Vec", Job::Vec);
 
     py::class_<Comm, std::shared_ptr<Comm>>(m, "Comm")
@@ -554,6 +563,35 @@ PYBIND11_MODULE(_slate, m) {
         slate_hip_call(hipStreamSynchronize(c.stream));
     });
     m.def("lowprec_gemm_calls", &lb::lowprec_gemm_calls);
+    m.def("hetrd_stats", []() {
+        const HetrdStats st = hetrd_stats();
+        py::dict r;
+        r["columns"] = st.columns;
+        r["panels"] = st.panels;
+        r["host_syncs"] = st.host_syncs;
+        r["launches_column"] = st.launches_column;
+        r["launches_larfg"] = st.launches_larfg;
+        r["launches_symv"] = st.launches_symv;
+        r["launches_correct"] = st.launches_correct;
+        r["ms_symv"] = st.ms_symv;
+        r["ms_panel"] = st.ms_panel;
+        r["ms_syr2k"] = st.ms_syr2k;
+        r["ms_larft"] = st.ms_larft;
+        return r;
+    });
+    // y = A x from the lower triangle of the order-m block at A (device pointers)
+    // (repeat: the product is enqueued that many times before the one synchronisation, for timing)
+    m.def("lb_symv_lower", [](std::string type, int64_t mm, uintptr_t A, int64_t lda, uintptr_t x, uintptr_t y,
+                              int repeat) {
+        if (type != "d" && type != "s") throw Exception("symv_lower: float32 or float64");
+        py::gil_scoped_release r;
+        auto c = lb::Ctx::device(ops_queue());
+        for (int k = 0; k < std::max(repeat, 1); ++k) {
+            if (type == "d") lb::symv_lower<double>(c, mm, (double const*)A, lda, (double const*)x, (double*)y);
+            else lb::symv_lower<float>(c, mm, (float const*)A, lda, (float const*)x, (float*)y);
+        }
+        slate_hip_call(hipStreamSynchronize(c.stream));
+    });
     m.def("bdsdc_stats", []() {
         const BdsdcStats st = bdsdc_stats();
         py::dict r;

@@ -336,6 +336,12 @@ void bind_drivers(py::module_& m, std::string const& s) {
         Options op = to_options(o); Matrix<T> U = opt_mat(u), VT = opt_mat(vt);
         { py::gil_scoped_release r; bdsdc(ju, jv, D, E, U, VT, op); }
         return D; });
+    DEF("hetrd", [](HermitianMatrix<T>& A, py::dict o) {
+        Options op = to_options(o); std::vector<R> D, E; TriangularFactors<T> Tf;
+        { py::gil_scoped_release r; hetrd(A, D, E, Tf, op); }
+        return py::make_tuple(D, E, Tf); });
+    DEF("unmtr_hetrd", [](Side sd, Op op_, HermitianMatrix<T>& A, TriangularFactors<T> Tf, Matrix<T>& C, py::dict o) {
+        Options op = to_options(o); py::gil_scoped_release r; unmtr_hetrd(sd, op_, A, Tf, C, op); });
     DEF("gels_cholqr", [](Matrix<T>& A, Matrix<T>& Rm, Matrix<T>& BX, py::dict o) {
         Options op = to_options(o); py::gil_scoped_release r; gels_cholqr(A, Rm, BX, op); });
     DEF("gels_qr", [](Matrix<T>& A, Matrix<T>& BX, py::dict o) {

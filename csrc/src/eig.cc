@@ -725,10 +725,81 @@ void rescale_values(std::vector<R>& v, R anorm, R alpha) {
     for (auto& x : v) x = x / alpha * anorm;   // divide first: x / alpha stays in range
 }
 
+/// heev with MethodHetrd::OneStage after the range guard: F holds the scaled
+/// lower triangle on a grid of one process.  hetrd on F's local block, then
+/// sterf, or the tridiagonal eigenvectors into Qt, copied to Z's layout and
+/// multiplied by Q panel by panel.
+template <typename R>
+void heev_one_stage(Matrix<R>& F, std::vector<R>& Lambda, Matrix<R>& Z, R anorm, R alpha, int64_t nb,
+                    Options const& opts) {
+    const Target target = resolve_target(opts);
+    const Loc loc = loc_of(target);
+    const int64_t n = F.n();
+    lb::Ctx c = target == Target::Devices ? lb::Ctx::device(0) : lb::Ctx::host();
+    LocalBlock<R> lf = F.local(loc, true);
+    slate_error_if_msg(lf.m != n || lf.n != n, "heev: one-stage reduction needs the whole matrix in one local block");
+    Work<R> tau(target, size_t(n)), Tfac(target, size_t(kHetrdPanel) * n);
+    std::vector<R> d, e;
+    {
+        trace::Block t2("hetrd");
+        hetrd_local<R>(c, n, lf.ptr, lf.ld, d, e, tau.data(), Tfac.data());
+    }
+    if (!wanted(Z)) {
+        trace::Block t2("sterf");
+        host::sterf<R>(n, d.data(), e.data());
+        Lambda = d;
+        rescale_values(Lambda, anorm, alpha);
+        return;
+    }
+    const int64_t me = get_option<int64_t>(opts, Option::MethodEig, int64_t(MethodEig::DC));
+    const bool use_qr = (me == int64_t(MethodEig::QR) || me == 'q');
+    const int64_t nbq = std::max<int64_t>(std::min<int64_t>(nb, eig_band_width()), std::min<int64_t>(nb, 512));
+    Matrix<R> Qt(n, n, nbq, nbq, F.grid());
+    Qt.insertLocalTiles(target);
+    // T to unit max-norm (as LAPACK's stedc does): a matrix at the edge of the
+    // range guard leaves T near sqrt(safe_min / eps), where the secular
+    // equation's products of differences underflow
+    R tmax = R(0);
+    for (R x : d) tmax = std::max(tmax, std::abs(x));
+    for (R x : e) tmax = std::max(tmax, std::abs(x));
+    if (tmax > R(0)) {
+        for (R& x : d) x /= tmax;
+        for (R& x : e) x /= tmax;
+    }
+    {
+        trace::Block t2("tridiag_eig");
+        if (use_qr) {
+            set(R(0), R(1), Qt, opts);
+            steqr2_dist<R>(d, e, Qt, opts);
+        } else {
+            stedc_dist<R>(d, e, Qt, opts);
+        }
+    }
+    if (tmax > R(0)) for (R& x : d) x *= tmax;
+    Lambda = d;
+    rescale_values(Lambda, anorm, alpha);
+    trace::Block t2("unmtr_hetrd");
+    slate::copy<R, R>(Qt, Z, opts);
+    Qt = Matrix<R>();
+    slate_error_if_msg(Z.op() != Op::NoTrans || !Z.aligned(), "heev: one-stage reduction needs a whole NoTrans Z");
+    LocalBlock<R> lz = Z.local(loc, true);
+    unmtr_hetrd_local<R>(c, Side::Left, Op::NoTrans, n, lf.ptr, lf.ld, Tfac.data(), n, Z.n(), lz.ptr, lz.ld);
+    if (c.dev()) slate_hip_call(hipStreamSynchronize(c.stream));
+    finish_origin(Z, opts);
+}
+
 }  // namespace
 
 template <typename T>
 void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts) {
+    const int64_t mh = get_option<int64_t>(opts, Option::MethodHetrd, int64_t(MethodHetrd::TwoStage));
+    slate_error_if_msg(mh != int64_t(MethodHetrd::TwoStage) && mh != int64_t(MethodHetrd::OneStage),
+                       "heev: Option::MethodHetrd is neither MethodHetrd::TwoStage nor MethodHetrd::OneStage");
+    const bool one_stage = mh == int64_t(MethodHetrd::OneStage);
+    if (one_stage) {
+        internal::hetrd_check_operand<T>(A, "heev", "A");
+        if (wanted(Z)) internal::hetrd_check_operand<T>(Z, "heev", "Z");
+    }
     {   // multi-device A (and Z): on its devices
         bool ran = internal::spread<T>(opts, {{&A, true}, {&Z, true}}, [&](std::vector<Matrix<T>>& M, int r) {
             auto H = internal::rewrap(A, M[0]);
@@ -775,6 +846,10 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
         else slate::copy<T, T>(conj_transpose(Ag), F, opts);   // upper: mirror into the lower triangle
     }
     if (alpha != R(1)) scale(alpha, anorm, F, opts);
+    if (one_stage) {
+        if constexpr (!is_complex_v<T>) heev_one_stage(F, Lambda, Z, anorm, alpha, A.nb(), opts);
+        return;
+    }
     const int64_t nt = F.nt();
     std::vector<TriangularFactors<T>> Ts;
     he2hb(F, Ts, opts);

@@ -1005,5 +1005,89 @@ template int64_t stedc<double>(int64_t, double*, double*, double*, int64_t);
 SLATE_STEDC_INST(float)
 SLATE_STEDC_INST(double)
 
+//------------------------------------------------------------------------------
+// One-stage tridiagonal reduction (LAPACK sytrd / latrd from the math), the
+// host twin of kernels/hetrd.hip: the same five steps per column.
+template <typename R>
+void hetrd(int64_t n, R* A, int64_t lda, R* d, R* e, R* tau, int64_t nb) {
+    if (n <= 0) return;
+    nb = std::max<int64_t>(1, nb);
+    std::vector<R> W(size_t(n) * nb), tv(nb), tw(nb), w(n);
+    for (int64_t j0 = 0; j0 < n - 1; j0 += nb) {
+        const int64_t kb = std::min(nb, n - 1 - j0);
+        for (int64_t c = 0; c < kb; ++c) {
+            const int64_t i = j0 + c;
+            // 1: A(i:n, i) -= V W(i,:)^T + W V(i,:)^T
+            for (int64_t k = 0; k < c; ++k) {
+                const R wi = W[i + k * n], vi = A[i + (j0 + k) * lda];
+                const R* vk = A + (j0 + k) * lda;
+                const R* wk = W.data() + k * n;
+                for (int64_t r = i; r < n; ++r) A[r + i * lda] -= vk[r] * wi + wk[r] * vi;
+            }
+            d[i] = A[i + i * lda];
+            // 2: larfg of A(i+1:n, i); the unit entry is stored
+            R* v = A + i * lda;
+            R ss = 0;
+            for (int64_t r = i + 2; r < n; ++r) ss += v[r] * v[r];
+            const R alpha = v[i + 1];
+            R beta = alpha, t = 0;
+            if (ss != R(0)) {
+                const R nrm = std::sqrt(alpha * alpha + ss);
+                beta = alpha >= R(0) ? -nrm : nrm;
+                t = (beta - alpha) / beta;
+                const R sc = R(1) / (alpha - beta);
+                for (int64_t r = i + 2; r < n; ++r) v[r] *= sc;
+            }
+            v[i + 1] = R(1);
+            e[i] = beta;
+            tau[i] = t;
+            // 3: w = A(i+1:n, i+1:n) v from the lower triangle: the column
+            // dots, then the rows by blocks (each block walks its columns)
+            const int64_t o = i + 1;
+            #pragma omp parallel for schedule(dynamic, 16)
+            for (int64_t j = o; j < n; ++j) {
+                const R* aj = A + j * lda;
+                R s = 0;
+                for (int64_t r = j; r < n; ++r) s += aj[r] * v[r];
+                w[j] = s;
+            }
+            #pragma omp parallel for schedule(dynamic, 1)
+            for (int64_t rb = o; rb < n; rb += 256) {
+                const int64_t re = std::min(n, rb + 256);
+                for (int64_t j = o; j < re - 1; ++j) {
+                    const R* aj = A + j * lda;
+                    const R vj = v[j];
+                    for (int64_t r = std::max(rb, j + 1); r < re; ++r) w[r] += aj[r] * vj;
+                }
+            }
+            // 4: w -= V (W^T v) + W (V^T v)
+            for (int64_t k = 0; k < c; ++k) {
+                const R* vk = A + (j0 + k) * lda;
+                const R* wk = W.data() + k * n;
+                R sv = 0, sw = 0;
+                for (int64_t r = o; r < n; ++r) { sv += vk[r] * v[r]; sw += wk[r] * v[r]; }
+                tv[k] = sv; tw[k] = sw;
+            }
+            for (int64_t k = 0; k < c; ++k) {
+                const R* vk = A + (j0 + k) * lda;
+                const R* wk = W.data() + k * n;
+                for (int64_t r = o; r < n; ++r) w[r] -= vk[r] * tw[k] + wk[r] * tv[k];
+            }
+            // 5: w = tau (w - (tau / 2)(w^T v) v)
+            R dot = 0;
+            for (int64_t r = o; r < n; ++r) dot += w[r] * v[r];
+            const R a2 = R(0.5) * t * t * dot;
+            for (int64_t r = o; r < n; ++r) W[r + c * n] = t * w[r] - a2 * v[r];
+        }
+        // trailing update, lower triangle
+        const int64_t k1 = j0 + kb;
+        rank2k(false, Uplo::Lower, Op::NoTrans, n - k1, kb, R(-1), A + k1 + j0 * lda, lda, W.data() + k1, n, R(1),
+               A + k1 + k1 * lda, lda);
+    }
+    d[n - 1] = A[(n - 1) + (n - 1) * lda];
+}
+template void hetrd<float>(int64_t, float*, int64_t, float*, float*, float*, int64_t);
+template void hetrd<double>(int64_t, double*, int64_t, double*, double*, double*, int64_t);
+
 }  // namespace host
 }  // namespace slate

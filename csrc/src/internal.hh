@@ -306,6 +306,28 @@ template <typename T>
 void bdsdc_place(lb::Ctx const& c, Matrix<T>& A, real_type<T> const* src, int64_t lds, bool trans,
                  std::vector<T> const& phase);
 
+/// Panel width of the one-stage tridiagonal reduction (hetrd.cc); its T
+/// factors are kHetrdPanel x kHetrdPanel blocks, panel p at column p * kHetrdPanel.
+constexpr int64_t kHetrdPanel = 64;
+/// One-stage tridiagonal reduction of the lower triangle of the contiguous
+/// local n x n array A (c's memory): A = Q T Q^T, T = tridiag(d, e) with
+/// signed e, reflectors left in A below the subdiagonal with their unit entry
+/// stored, tau (n) and Tfac (kHetrdPanel x n) in c's memory, d and e on the
+/// host.  One host synchronisation, at the end.  The strict upper triangle is
+/// not read.
+template <typename R>
+void hetrd_local(lb::Ctx const& c, int64_t n, R* A, int64_t lda, std::vector<R>& d, std::vector<R>& e, R* tau,
+                 R* Tfac);
+/// C (mc x nc) := op(Q) C (Left) or C op(Q) (Right), Q = H_0 .. H_{n-2} of
+/// hetrd_local, one lb::larfb per panel; stream-ordered on the device.
+template <typename R>
+void unmtr_hetrd_local(lb::Ctx const& c, Side side, Op op, int64_t n, R const* A, int64_t lda, R const* Tfac,
+                       int64_t mc, int64_t nc, R* C, int64_t ldc);
+/// slate::NotImplemented unless the one-stage reduction can take this operand
+/// (real type, one process, one device, block-cyclic); `who` names the routine
+template <typename T>
+void hetrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
+
 /// Apply LU pivots to the rows of B (forward: P B; backward: P^T B).
 template <typename T>
 void apply_pivots(Pivots const& pivots, BaseMatrix<T> const& A, Matrix<T>& B, Target target, bool forward);

@@ -61,6 +61,9 @@ struct Params {
     // --method-svd qr|dc: Option::MethodSVD of svd
     bool has_method_svd = false;
     MethodSVD method_svd = MethodSVD::QR;
+    // --method-hetrd two_stage|one_stage: Option::MethodHetrd of heev
+    bool has_method_hetrd = false;
+    MethodHetrd method_hetrd = MethodHetrd::TwoStage;
     // operand shape flags of the BLAS-3 / triangular routines (reference
     // --uplo --trans --side --diag)
     Uplo uplo = Uplo::Lower;
@@ -1344,6 +1347,50 @@ Result r_he2hb(Case<T>& c, int variant) {   // 0 he2hb (A = Q B Q^H), 1 unmtr_he
 }
 
 template <typename T>
+Result r_hetrd(Case<T>& c, int variant) {   // 0 hetrd (A = Q T Q^T), 1 unmtr_hetrd (Q (Q^T C) = C)
+    using R = R_<T>;
+    if (is_complex_v<T>) {
+        Result r; r.skipped = true; r.note = "real types (the one-stage reduction)"; return r;
+    }
+    auto Ag = herm_of(c, c.n);
+    if (Ag.grid()->size() != 1) {
+        Result r; r.skipped = true; r.note = "a grid of one process (the one-stage reduction)"; return r;
+    }
+    auto A0 = c.copy_of(Ag);
+    HermitianMatrix<T> A(Uplo::Lower, Ag);
+    std::vector<R> d, e;
+    TriangularFactors<T> Tf;
+    Result r;
+    const double n = double(c.n);
+    if (variant == 0) {
+        r.time = c.timed([&] { hetrd(A, d, e, Tf, c.opts); });
+        r.flops = cfac<T>() * 4.0 / 3 * n * n * n;
+        if (c.P.check) {
+            auto F = c.zeros(c.n, c.n);
+            set<T>(std::function<T(int64_t, int64_t)>([&](int64_t i, int64_t j) {
+                       return i == j ? T(d[i]) : (i == j + 1 ? T(e[j]) : (j == i + 1 ? T(e[i]) : T(0)));
+                   }), F, Options{{Option::Target, Target::Host}});
+            unmtr_hetrd(Side::Left, Op::NoTrans, A, Tf, F, c.opts);
+            unmtr_hetrd(Side::Right, Op::ConjTrans, A, Tf, F, c.opts);
+            add(T(-1), A0, T(1), F, c.opts);
+            r.error = c.nrm(F) / (n * c.nrm(A0));
+        }
+        return r;
+    }
+    hetrd(A, d, e, Tf, c.opts);
+    auto C = c.mat(c.n, c.P.nrhs);
+    auto C0 = c.copy_of(C);
+    r.time = c.timed([&] { unmtr_hetrd(Side::Left, Op::ConjTrans, A, Tf, C, c.opts); });
+    r.flops = cfac<T>() * 2.0 * n * n * c.P.nrhs;
+    if (c.P.check) {
+        unmtr_hetrd(Side::Left, Op::NoTrans, A, Tf, C, c.opts);
+        add(T(-1), C0, T(1), C, c.opts);
+        r.error = c.nrm(C) / (n * c.nrm(C0));
+    }
+    return r;
+}
+
+template <typename T>
 Result r_hb2st(Case<T>& c, int variant) {   // 0 hb2st (Frobenius norm preserved), 1 unmtr_hb2st
     using R = R_<T>;
     auto A = herm_of(c, c.n);
@@ -1912,6 +1959,8 @@ std::map<std::string, Fn<T>> routines() {
         {"redistribute", [](Case<T>& c) { return r_aux<T>(c, 7); }},
         {"he2hb", [](Case<T>& c) { return r_he2hb<T>(c, 0); }},
         {"unmtr_he2hb", [](Case<T>& c) { return r_he2hb<T>(c, 1); }},
+        {"hetrd", [](Case<T>& c) { return r_hetrd<T>(c, 0); }},
+        {"unmtr_hetrd", [](Case<T>& c) { return r_hetrd<T>(c, 1); }},
         {"hb2st", [](Case<T>& c) { return r_hb2st<T>(c, 0); }},
         {"unmtr_hb2st", [](Case<T>& c) { return r_hb2st<T>(c, 1); }},
         {"ge2tb", r_ge2tb<T>},
@@ -1982,6 +2031,8 @@ int run_type(Params const& P, char tc, std::string const& name) {
                 if (with_precision) c.opts[Option::GemmPrecision] = P.gemm_precision;
                 const bool with_method_svd = P.has_method_svd && name == "svd";
                 if (with_method_svd) c.opts[Option::MethodSVD] = P.method_svd;
+                const bool with_method_hetrd = P.has_method_hetrd && name == "heev";
+                if (with_method_hetrd) c.opts[Option::MethodHetrd] = P.method_hetrd;
                 Result r;
                 std::string status;
                 try {
@@ -2004,7 +2055,10 @@ int run_type(Params const& P, char tc, std::string const& name) {
                     const std::string prec =
                         (with_precision ? std::string("  gemm_precision=") + to_string(P.gemm_precision) : "") +
                         (with_method_svd ? std::string("  method_svd=") + (P.method_svd == MethodSVD::DC ? "dc" : "qr")
-                                         : "");
+                                         : "") +
+                        (with_method_hetrd ? std::string("  method_hetrd=") +
+                                                 (P.method_hetrd == MethodHetrd::OneStage ? "one_stage" : "two_stage")
+                                           : "");
                     std::printf("%-16s %-4c %7lld %7lld %7lld %5lld %2d %2d %s %10.4f %11.2f  %s%s%s%s\n", name.c_str(),
                                 tc, (long long)c.m, (long long)c.n, (long long)c.k, (long long)nb, g->p(), g->q(), es,
                                 r.time, gf, status.c_str(), (r.note.empty() || r.skipped) ? "" : "  ",
@@ -2036,6 +2090,7 @@ void usage() {
         "       [--uplo l|u] [--trans n|t|c] [--side l|r] [--diag n|u] [--cond C] [--ib IB]\n"
         "       [--nonuniform-nb y|n] [--go c|r] [--do r|c]\n"
         "       [--gemm-precision native|bf16|bf16x3|bf16x6] [--method-svd qr|dc]\n"
+        "       [--method-hetrd two_stage|one_stage]\n"
         "routines:");
     for (auto const& kv : routines<double>()) std::printf(" %s", kv.first.c_str());
     std::printf("\n");
@@ -2102,6 +2157,15 @@ int main(int argc, char** argv) {
             if (v != "qr" && v != "dc") { std::fprintf(stderr, "--method-svd: qr or dc\n"); usage(); return 2; }
             P.method_svd = v == "dc" ? MethodSVD::DC : MethodSVD::QR;
             P.has_method_svd = true;
+        }
+        else if (a == "--method-hetrd") {
+            std::string v = val();
+            for (auto& ch : v) ch = char(std::tolower((unsigned char)ch));
+            if (v != "two_stage" && v != "one_stage") {
+                std::fprintf(stderr, "--method-hetrd: two_stage or one_stage\n"); usage(); return 2;
+            }
+            P.method_hetrd = v == "one_stage" ? MethodHetrd::OneStage : MethodHetrd::TwoStage;
+            P.has_method_hetrd = true;
         }
         else if (!a.empty() && a[0] != '-') rlist = rlist.empty() ? a : rlist + "," + a;
         else { usage(); return 2; }

@@ -15,6 +15,7 @@ Op = _slate.Op
 Uplo = _slate.Uplo
 Job = _slate.Job
 MethodSVD = _slate.MethodSVD
+MethodHetrd = _slate.MethodHetrd
 Diag = _slate.Diag
 Side = _slate.Side
 Norm = _slate.Norm

@@ -6,7 +6,7 @@ from ._wrap import call
 __all__ = ["heev", "hegv", "hegst", "svd", "svd_vals", "gesvd", "eig", "eig_vals", "he2hb", "hb2st", "sterf",
            "steqr", "stedc", "ge2tb", "tb2bd", "bdsqr", "syev", "sygv", "hb2st_band", "unmtr_hb2st",
            "unmtr_he2hb", "tb2bd_band", "unmbr_tb2bd", "unmbr_ge2tb", "steqr2", "stedc_matrix", "bdsqr_matrix",
-           "bdsdc", "bdsdc_matrix"]
+           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd"]
 
 
 def heev(A, Z=None, target=None, **kw):
@@ -163,3 +163,18 @@ def bdsdc_matrix(jobu, jobvt, d, e, U=None, VT=None, target=None, **kw):
     import numpy as np
     key = U if U is not None else VT
     return np.asarray(call("bdsdc_mat", key, jobu, jobvt, list(d), list(e), U, VT, target=target, **kw))
+
+
+def hetrd(A, target=None, **kw):
+    """One-stage tridiagonal reduction of the lower triangle of a real
+    symmetric / Hermitian matrix of one process: returns (d, e, T) with
+    A = Q tridiag(d, e) Q^T, e signed; the reflectors stay in A, T holds the
+    block-reflector factors for unmtr_hetrd."""
+    import numpy as np
+    d, e, T = call("hetrd", A, A, target=target, **kw)
+    return np.asarray(d), np.asarray(e), T
+
+
+def unmtr_hetrd(side, op, A, T, C, target=None, **kw):
+    """C := op(Q) C (Side.Left) or C op(Q) (Side.Right) with Q from hetrd(A)."""
+    return call("unmtr_hetrd", C, side, op, A, T, C, target=target, **kw)

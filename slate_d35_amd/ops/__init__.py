@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "symv_lower", "hetrd_stats", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -82,6 +82,38 @@ def bdsdc_stats() -> dict:
     (in all and per tree level, root first) and the launches of the three
     device kernels (zero on the host target)."""
     return _slate.bdsdc_stats()
+
+
+def hetrd_stats() -> dict:
+    """Counters of the last one-stage tridiagonal reduction of this process
+    (hetrd, or heev with method_hetrd="one_stage"): `columns`, `panels`,
+    `host_syncs` inside the reduction and the launches of its four column
+    kernels, launches_column / _larfg / _symv / _correct (zero on the host
+    target).  ms_symv / ms_panel / ms_syr2k / ms_larft are device milliseconds
+    from events between the kernels, recorded only when SLATE_HETRD_PROFILE=1
+    is in the environment (zero otherwise)."""
+    return _slate.hetrd_stats()
+
+
+def symv_lower(A, x, offset: int = 0, repeat: int = 1):
+    """y = S x on the device, S the symmetric block of the column-major matrix
+    A that starts at (offset, offset), read from its lower triangle only: the
+    strict upper triangle is never loaded.  float32 or float64; returns y
+    (order of A less offset).  Two calls give the same bits.  repeat > 1
+    enqueues the same product that many times before the one synchronisation
+    (timing)."""
+    import torch
+    pa, rows, cols, lda = _cm(A)
+    m = cols - offset
+    assert 0 <= offset and m >= 0 and rows >= cols and x.numel() == m and x.dtype == A.dtype and x.is_contiguous()
+    if x.is_cuda:
+        torch.cuda.current_stream(x.device).synchronize()
+    y = torch.empty(m, dtype=A.dtype, device=A.device)
+    torch.cuda.current_stream(A.device).synchronize()
+    if m > 0:
+        _slate.lb_symv_lower(_suffix(A), m, pa + (offset + offset * lda) * A.element_size(), lda, x.data_ptr(),
+                             y.data_ptr(), repeat)
+    return y
 
 
 def gemm_async(queue: int, opA: str, opB: str, alpha, A, B, beta, C):

@@ -81,8 +81,14 @@ class Ctx:
         ms = getattr(self.a, "method_svd", None)
         return ms if ms and self.name == "svd" else None
 
+    def method_hetrd(self):
+        mh = getattr(self.a, "method_hetrd", None)
+        return mh if mh and self.name == "heev" else None
+
     def opts(self):
         o = dict(target=self.target, lookahead=self.a.lookahead)
+        if self.method_hetrd():
+            o["method_hetrd"] = self.method_hetrd()
         if self.gemm_precision():
             o["gemm_precision"] = self.gemm_precision()
         if self.method_svd():
@@ -268,6 +274,49 @@ def r_heev(c):
     return t, err
 
 
+def _sym(c):
+    a, _ = c.mat(c.n, c.n)
+    a = ((a + a.conj().T) / 2).astype(c.dt)
+    return a, core.from_numpy(a, nb=c.nb, target=c.target)
+
+
+def _tridiag(d, e):
+    return np.diag(d) + np.diag(e, 1) + np.diag(e, -1)
+
+
+def _real_only(c):
+    if np.iscomplexobj(np.zeros(1, c.dt)):
+        raise NotImplementedError("real types (the one-stage reduction)")
+
+
+def r_hetrd(c):
+    _real_only(c)
+    a, A = _sym(c)
+    H = core.HermitianMatrix(core.Uplo.Lower, A)
+    t, (d, e, T) = _timed(lambda: M.hetrd(H, target=c.target))
+    err = None
+    if c.a.check:
+        Q = core.from_numpy(np.eye(c.n, dtype=c.dt), nb=c.nb, target=c.target)
+        M.unmtr_hetrd(core.Side.Left, core.Op.NoTrans, H, T, Q, target=c.target)
+        q = core.to_numpy(Q)
+        err = np.linalg.norm(q @ _tridiag(d, e) @ q.conj().T - a) / (np.linalg.norm(a) * c.n)
+    return t, err
+
+
+def r_unmtr_hetrd(c):
+    _real_only(c)
+    a, A = _sym(c)
+    H = core.HermitianMatrix(core.Uplo.Lower, A)
+    d, e, T = M.hetrd(H, target=c.target)
+    b, C = c.mat(c.n, c.a.nrhs)
+    t, _ = _timed(lambda: M.unmtr_hetrd(core.Side.Left, core.Op.ConjTrans, H, T, C, target=c.target))
+    err = None
+    if c.a.check:
+        M.unmtr_hetrd(core.Side.Left, core.Op.NoTrans, H, T, C, target=c.target)
+        err = resid(core.to_numpy(C), b)
+    return t, err
+
+
 def r_svd(c):
     a, A = c.mat(c.m, c.n)
     k = min(c.m, c.n)
@@ -342,6 +391,8 @@ ROUTINES = {
     "geqrf": (r_geqrf, lambda m, n, k: F.geqrf_flops(m, n)),
     "gels": (r_gels, lambda m, n, k: F.geqrf_flops(m, n)),
     "heev": (r_heev, lambda m, n, k: 4.0 / 3.0 * n ** 3),
+    "hetrd": (r_hetrd, lambda m, n, k: 4.0 / 3.0 * n ** 3),
+    "unmtr_hetrd": (r_unmtr_hetrd, lambda m, n, k: 0.0),
     "svd": (r_svd, lambda m, n, k: 8.0 / 3.0 * n ** 3),
     "hesv": (r_hesv, lambda m, n, k: n ** 3 / 3.0),
     "gbsv": (r_gbsv, lambda m, n, k: 0.0),
@@ -368,6 +419,8 @@ def main(argv=None):
                     help="arithmetic of the fp32 trailing updates of gemm, getrf*, potrf and the mixed solvers")
     ap.add_argument("--method-svd", default=None, choices=["qr", "dc"],
                     help="bidiagonal stage of svd: QR iteration (default) or divide and conquer")
+    ap.add_argument("--method-hetrd", default=None, choices=["two_stage", "one_stage"],
+                    help="tridiagonal reduction of heev: two stages (default) or the one-stage hetrd")
     a = ap.parse_args(argv)
     a.check = a.check.lower().startswith("y")
     world = parallel.world_size()
@@ -407,7 +460,8 @@ def main(argv=None):
                             print(f"{name:18s} {tch:4s} {c.m:6d} {c.n:6d} {c.k:6d} {nb:5d} {p:2d} {q:2d} "
                                   f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}"
                                   + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else "")
-                                  + (f"  method_svd={c.method_svd()}" if c.method_svd() else ""),
+                                  + (f"  method_svd={c.method_svd()}" if c.method_svd() else "")
+                                  + (f"  method_hetrd={c.method_hetrd()}" if c.method_hetrd() else ""),
                                   flush=True)
     if rank == 0:
         print(f"# {nfail} failed" if nfail else "# all tests passed")
