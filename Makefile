@@ -36,7 +36,7 @@ all: $(LIB) $(PYMOD) $(LAPACK_API) $(SCALAPACK_API)
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/k_%.o: csrc/kernels/%.hip csrc/kernels/*.hh | $(BUILD)
+$(BUILD)/k_%.o: csrc/kernels/%.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/s_%.o: csrc/src/%.cc $(HDRS) | $(BUILD)

@@ -1,7 +1,9 @@
-// Secular-equation root finder shared by the host divide-and-conquer
-// (eig_host.cc stedc_secular, eig_dist.cc secular_host) and the device
-// kernel (kernels/stedc.hip secular_roots_kernel): one definition, compiled
-// by g++ for the host and by hipcc for gfx950 (reference src/stedc_secular.cc
+// Secular-equation arithmetic shared by the host divide-and-conquer
+// (eig_host.cc stedc_secular, dc_merge.cc) and the device kernels
+// (kernels/dc_merge.hip): the root finder, the pole families of the
+// tridiagonal (LinearPoles) and the bidiagonal (SquaredPoles) merge, the
+// strided secular sums and the z-hat entry -- one definition, compiled by
+// g++ for the host and by hipcc for gfx950 (reference src/stedc_secular.cc
 // calls LAPACK laed4 per root; this is the same rational "middle way"
 // iteration, written from its derivation below, with a bisection safeguard).
 //
@@ -66,9 +68,9 @@ SLATE_SECULAR_FN Sums<R> sums(int64_t k, int64_t j, const R* d, const R* z, int6
 
 /// The iteration itself, on poles known only through their differences:
 /// diff(i, o) = pole_i - pole_o.  root_with passes d[i] - d[o]; the bidiagonal
-/// divide and conquer (kernels/bdsdc.hip) has poles d_i^2 and passes the
-/// product (d_i - d_o)(d_i + d_o), so no difference of squared values is ever
-/// formed; its sum_fn builds delta_i from the same product.
+/// divide and conquer has poles d_i^2 and passes the product
+/// (d_i - d_o)(d_i + d_o) (SquaredPoles below), so no difference of squared
+/// values is ever formed; its sum_fn builds delta_i from the same product.
 template <typename R, typename DiffFn, typename SumFn>
 SLATE_SECULAR_FN R root_core(int64_t k, int64_t j, R rho, R znorm2, int64_t* org, DiffFn&& diff, SumFn&& sum_fn) {
     const R eps = std::numeric_limits<R>::epsilon();
@@ -141,6 +143,80 @@ template <typename R>
 SLATE_SECULAR_FN R sqrt_shift(R d_o, R t) {
     const R den = std::sqrt(std::fmax(d_o * d_o + t, R(0))) + d_o;
     return den > R(0) ? t / den : R(0);
+}
+
+/// Pole families of the two merges.  Each holds the pole array d (ascending)
+/// and gives, in one fixed operand order:
+///   diff(i, o)                pole_i - pole_o (root_core);
+///   delta(i, d0, t)           pole_i - pole_o - t with d0 = d[o], the
+///                             denominator of the secular sums;
+///   shift(o, t)               the converged shift as tau, root = d[o] + tau;
+///   root_minus_pole(o, tau, i)   root (o, tau) minus pole i (z-hat);
+///   pole_minus_root(i, dr, tr)   pole i minus root (dr = d[o], tr = tau), the
+///                             denominator of a secular vector entry.
+/// LinearPoles: pole d_i (stedc).
+template <typename R>
+struct LinearPoles {
+    const R* d;
+    SLATE_SECULAR_FN R diff(int64_t i, int64_t o) const { return d[i] - d[o]; }
+    SLATE_SECULAR_FN R delta(int64_t i, R d0, R t) const { return (d[i] - d0) - t; }
+    SLATE_SECULAR_FN R shift(int64_t, R t) const { return t; }
+    SLATE_SECULAR_FN R root_minus_pole(int64_t o, R tau, int64_t i) const { return (d[o] - d[i]) + tau; }
+    SLATE_SECULAR_FN R pole_minus_root(int64_t i, R dr, R tr) const { return (d[i] - dr) - tr; }
+};
+
+/// SquaredPoles: pole d_i^2, root sigma^2 (bdsdc), known only through
+/// (d_i - d_o)(d_i + d_o); tau = sigma - d_o.
+template <typename R>
+struct SquaredPoles {
+    const R* d;
+    SLATE_SECULAR_FN R diff(int64_t i, int64_t o) const { return (d[i] - d[o]) * (d[i] + d[o]); }
+    SLATE_SECULAR_FN R delta(int64_t i, R d0, R t) const { return (d[i] - d0) * (d[i] + d0) - t; }
+    SLATE_SECULAR_FN R shift(int64_t o, R t) const { return sqrt_shift(d[o], t); }
+    SLATE_SECULAR_FN R root_minus_pole(int64_t o, R tau, int64_t i) const {
+        const R dorg = d[o], di = d[i];
+        return ((dorg - di) + tau) * ((dorg + di) + tau);
+    }
+    SLATE_SECULAR_FN R pole_minus_root(int64_t i, R dr, R tr) const {
+        const R di = d[i];
+        return ((di - dr) - tr) * ((di + dr) + tr);
+    }
+};
+
+/// The terms i = first, first + stride, ... of psi / phi and their derivatives
+/// at shifted point t (origin pole o): all of them with (0, 1); a wave passes
+/// (lane, 64) and adds the lanes' partial sums.
+template <typename R, typename Poles>
+SLATE_SECULAR_FN Sums<R> partial_sums(Poles const& p, int64_t k, int64_t j, const R* z, int64_t o, R t, int64_t first,
+                                      int64_t stride) {
+    Sums<R> s;
+    const R d0 = p.d[o];
+    for (int64_t i = first; i < k; i += stride) {
+        const R r = z[i] / p.delta(i, d0, t);
+        if (i <= j) { s.psi += z[i] * r; s.dpsi += r * r; }
+        else { s.phi += z[i] * r; s.dphi += r * r; }
+    }
+    return s;
+}
+
+/// tau of root j on a pole family; sum_fn(o, t) -> Sums<R> as for root_with.
+template <typename R, typename Poles, typename SumFn>
+SLATE_SECULAR_FN R root_of(Poles const& p, int64_t k, int64_t j, R rho, R znorm2, int64_t* org, SumFn&& sum_fn) {
+    const R t = root_core<R>(k, j, rho, znorm2, org, [p](int64_t i, int64_t o) { return p.diff(i, o); }, sum_fn);
+    return p.shift(*org, t);
+}
+
+/// Entry i of z recomputed from the roots (Loewner / Gu-Eisenstat):
+/// zh_i^2 = prod_j (root_j - pole_i) / (rho prod_{j != i} (pole_j - pole_i)),
+/// with the sign of z_i.  The bidiagonal merge has rho = 1.
+template <typename R, typename Poles>
+SLATE_SECULAR_FN R zhat_entry(Poles const& p, int64_t k, int64_t i, R rho, const R* z, const int64_t* org,
+                              const R* tau) {
+    R pr = p.root_minus_pole(org[k - 1], tau[k - 1], i) / rho;
+    // the select is on the differences, not on the index: j is uniform over a wave, so both poles are scalar loads
+    for (int64_t j = 0; j < k - 1; ++j)
+        pr *= p.root_minus_pole(org[j], tau[j], i) / (j < i ? p.diff(j, i) : p.diff(j + 1, i));
+    return std::copysign(std::sqrt(std::fabs(pr)), z[i]);
 }
 
 }  // namespace secular

@@ -12,6 +12,7 @@
 #include <cstdint>
 #include "dev_types.hh"
 #include "matgen_entry.hh"
+#include "slate_amd/secular.hh"
 
 namespace slate_amd {
 namespace dev {
@@ -100,51 +101,81 @@ void pplu_apply(int np, const T* gbuf, int64_t kb, int64_t j, int64_t cend, int6
                 int64_t lda, RowDist d, int64_t lr_k, int64_t kk, int pk, double thresh, bool is_pk, int64_t* pip,
                 int* info, int64_t info_off, hipStream_t s);
 
-// ---- distributed divide and conquer (stedc.hip)
-/// secular roots of D + rho z z^T (dd ascending, k of them): lambda_j = dd[org[j]] + tau[j]
-void secular_roots(int64_t k, double rho, const double* dd, const double* zz, double znorm2, int64_t* org,
-                   double* tau, hipStream_t s);
-/// Gu-Eisenstat z from the computed roots
-void gu_eisenstat(int64_t k, double rho, const double* dd, const double* zz, const int64_t* org, const double* tau,
-                  double* zh, hipStream_t s);
-/// one merge's device vectors and the local layout of the n2 x n2 block (see stedc.hip)
-struct StedcMerge {
-    int64_t n2 = 0, k = 0, nrot = 0;
+// ---- merge of the tridiagonal and the bidiagonal divide and conquer (dc_merge.hip)
+// One merge after sorting and deflation: n sorted-basis entries, k of them
+// active with poles dd (ascending).  Poles is slate::secular::LinearPoles
+// (stedc: D + rho z z^T, lambda_j = dd[org[j]] + tau[j]) or SquaredPoles
+// (bdsdc: 1 + sum z_i^2 / ((d_i - sigma)(d_i + sigma)), dd[0] = 0, rho = 1,
+// sigma_j = dd[org[j]] + tau[j]), holding the device pointer dd.
+/// secular roots, one wave per root
+template <typename Poles>
+void secular_roots(Poles poles, int64_t k, double rho, const double* zz, double znorm2, int64_t* org, double* tau,
+                   hipStream_t s);
+/// z recomputed from the computed roots (Loewner / Gu-Eisenstat)
+template <typename Poles>
+void zhat(Poles poles, int64_t k, double rho, const double* zz, const int64_t* org, const double* tau, double* zh,
+          hipStream_t s);
+/// the vectors of one merge: device pointers for merge_columns, host pointers for its host twin (dc_merge.cc).
+/// dd, zh, tau, org, act: k entries; defl: n - k; ord, inv_perm: n.  Result column r = ord[jo]: r < k the secular
+/// vector of root r, entry i at sorted index act[i], else the unit vector of sorted index defl[r - k].
+struct DcMerge {
+    int64_t n = 0, k = 0;
     const double *dd = nullptr, *zh = nullptr, *tau = nullptr;
     const int64_t *org = nullptr, *act = nullptr, *defl = nullptr, *ord = nullptr, *inv_perm = nullptr;
-    const int64_t* rot_ab = nullptr;
-    const double* rot_cs = nullptr;
+};
+/// recorded deflation rotations: pairs (a, b) and (c, s) in application order
+struct DcRotations {
+    int64_t nrot = 0;
+    const int64_t* ab = nullptr;
+    const double* cs = nullptr;
+};
+SLATE_HD inline int64_t bc_l2g(int64_t l, int64_t b, int64_t procs, int64_t rel) {
+    return ((l / b) * procs + rel) * b + l % b;
+}
+// Side policies of merge_columns.  result(c): the sorted result index jo that
+// output column c holds (jo >= n: a column outside the secular system, filled
+// with null_entry); entry(i, di, u): entry i of a secular vector before
+// normalisation; row_entry: what output row `row` takes from the finished
+// sorted-basis vector vec.
+/// stedc: the block-cyclic local rows / columns of the n x n block; view-relative global index = l2g(local) - off,
+/// and row src takes vec[inv_perm[src]]
+struct StedcSide {
+    using Poles = slate::secular::LinearPoles<double>;
     int64_t lrows = 0, mb = 1, p = 1, rrel = 0, row_off = 0;
     int64_t nb = 1, q = 1, crel = 0, col_off = 0;
-    int64_t lr0 = 0, lc0 = 0;
+    int64_t lr0 = 0, lc0 = 0;                      // first local row / column of the block
+    SLATE_HD int64_t rows(int64_t) const { return lrows; }
+    SLATE_HD int64_t result(int64_t lc) const { return bc_l2g(lc0 + lc, nb, q, crel) - col_off; }
+    SLATE_HD double null_entry(int64_t, int64_t) const { return 0.0; }   // not reached: result(lc) < n
+    SLATE_HD double entry(int64_t, double, double u) const { return u; }
+    SLATE_HD double row_entry(int64_t lr, int64_t, const double* vec, const int64_t* inv_perm) const {
+        return vec[inv_perm[bc_l2g(lr0 + lr, mb, p, rrel) - row_off]];
+    }
 };
-/// local columns [c_first, c_first + ncols) of the merge matrix into M (ld ldm); scratch: ncols * n2 reals
-template <typename T>
-void merge_matrix(StedcMerge const& m, int64_t c_first, int64_t ncols, T* M, int64_t ldm, double* scratch,
-                  hipStream_t s);
-
-// ---- bidiagonal divide and conquer (bdsdc.hip)
-/// roots of 1 + sum z_i^2 / ((d_i - sigma)(d_i + sigma)) (dd ascending, dd[0] = 0): sigma_j = dd[org[j]] + tau[j]
-void bdsdc_secular_roots(int64_t k, const double* dd, const double* zz, double znorm2, int64_t* org, double* tau,
-                         hipStream_t s);
-/// z recomputed from the roots (Loewner / Gu-Eisenstat)
-void bdsdc_zhat(int64_t k, const double* dd, const double* zz, const int64_t* org, const double* tau, double* zh,
-                hipStream_t s);
-/// one merge's device vectors (see bdsdc.hip); n sorted-basis entries, k of them not deflated, row nl of the
-/// block is the removed row / q1, row n (right side, sqre = 1) is q2, (qc, qs) the (q1, q2) rotation
-struct BdsdcMerge {
-    int64_t n = 0, k = 0, nl = 0, sqre = 0, nrot_u = 0, nrot_v = 0;
+/// bdsdc: dense MU (vside 0, n x n) or MV (vside 1, n + sqre square).  Row nl of the block is the removed row / q1,
+/// row n (right side, sqre = 1) is q2, (qc, qs) the (q1, q2) rotation: on the right side the special entry (sorted
+/// index 0, row nl) is the coefficient of qc q1 + qs q2, and column n the surviving null vector -qs q1 + qc q2.
+struct BdsdcSide {
+    using Poles = slate::secular::SquaredPoles<double>;
+    int64_t nl = 0, sqre = 0;
     double qc = 1, qs = 0;
-    const double *dd = nullptr, *zh = nullptr, *tau = nullptr;
-    const int64_t *org = nullptr, *act = nullptr, *defl = nullptr, *ord = nullptr, *inv_perm = nullptr;
-    const int64_t *rot_ab_u = nullptr, *rot_ab_v = nullptr;
-    const double *rot_cs_u = nullptr, *rot_cs_v = nullptr;
+    int vside = 0;
+    SLATE_HD int64_t rows(int64_t n) const { return n + (vside ? sqre : 0); }
+    SLATE_HD int64_t result(int64_t c) const { return c; }
+    SLATE_HD double null_entry(int64_t row, int64_t n) const { return row == nl ? -qs : (row == n ? qc : 0.0); }
+    SLATE_HD double entry(int64_t i, double di, double u) const { return vside ? u : (i == 0 ? -1.0 : di * u); }
+    SLATE_HD double row_entry(int64_t row, int64_t n, const double* vec, const int64_t* inv_perm) const {
+        if (row == n) return qs * vec[0];
+        const double v = vec[inv_perm[row]];
+        return (vside && row == nl) ? v * qc : v;
+    }
 };
-/// columns [c_first, c_first + ncols) of MU (vside false, n x n) or MV (n + sqre square) into M; scratch:
-/// ncols * n reals
-template <typename T>
-void bdsdc_merge_matrices(BdsdcMerge const& m, bool vside, int64_t c_first, int64_t ncols, T* M, int64_t ldm,
-                          double* scratch, hipStream_t s);
+/// output columns [c_first, c_first + ncols) of the merge matrix into M (ld ldm); scratch: ncols * m.n doubles
+template <typename T, typename Side>
+void merge_columns(DcMerge const& m, DcRotations const& rot, Side const& side, int64_t c_first, int64_t ncols, T* M,
+                   int64_t ldm, double* scratch, hipStream_t s);
+
+// ---- placement of the bidiagonal divide and conquer's factors (bdsdc.hip)
 /// block-cyclic local part (lrows x lcols) of op(src) with an optional row phase:
 /// dst(lr, lc) = phase[gi] * op(src)(gi, gj), gi = ((lr / mb) p + rrel) mb + lr % mb, gj likewise
 struct BdsdcPlace {

@@ -18,7 +18,8 @@
 //   M = [ z^T ; 0 diag(d_2 .. d_N) ],  z = (r0, alpha l1, beta f2), d_1 = 0.
 // Host, O(N): sort, three deflations (|z_i| tiny; d_i tiny: z_i rotated into
 // z_1 on the V side; two close d: one z rotated away on both sides; rotations
-// recorded, not applied).  Device (kernels/bdsdc.hip; host twins below):
+// recorded, not applied).  Then the merge shared with stedc_dist (dc_merge.hh;
+// device kernels/dc_merge.hip, host twins dc_merge.cc) on the poles d_i^2:
 // secular roots, z recomputed from the roots, the merge matrices MU / MV.
 // Then U := diag(U1, 1, U2) MU and V := diag(V1, V2) MV, two GEMMs each on
 // the local MFMA GEMM.  Leaves (<= SLATE_BDSDC_LEAF rows, default 64) run
@@ -28,8 +29,8 @@
 // Accuracy is absolute (eps ||B||): tiny singular values do not get the
 // relative accuracy of the QR iteration.
 #include "internal.hh"
+#include "dc_merge.hh"
 #include "slate_amd/eig_host.hh"
-#include "slate_amd/secular.hh"
 #include "../kernels/kernels.hh"
 
 #include <algorithm>
@@ -51,96 +52,7 @@ int64_t leaf_size() {
     return std::max<int64_t>(2, e ? std::atoll(e) : 64);
 }
 
-using slate_amd::dev::BdsdcMerge;
 using slate_amd::dev::BdsdcPlace;
-
-/// host twin of bdsdc_secular_roots + bdsdc_zhat
-void secular_host(int64_t k, std::vector<double> const& dd, std::vector<double> const& zz, double znorm2,
-                  std::vector<int64_t>& org, std::vector<double>& tau, std::vector<double>& zh) {
-    org.assign(k, 0); tau.assign(k, 0.0); zh.assign(k, 0.0);
-    const double* d = dd.data();
-    const double* z = zz.data();
-    #pragma omp parallel for schedule(dynamic, 8) if (k > 64)
-    for (int64_t j = 0; j < k; ++j) {
-        auto sum = [&](int64_t o, double t) {
-            secular::Sums<double> s;
-            const double d0 = d[o];
-            for (int64_t i = 0; i < k; ++i) {
-                const double r = z[i] / ((d[i] - d0) * (d[i] + d0) - t);
-                if (i <= j) { s.psi += z[i] * r; s.dpsi += r * r; }
-                else { s.phi += z[i] * r; s.dphi += r * r; }
-            }
-            return s;
-        };
-        auto diff = [d](int64_t i, int64_t o) { return (d[i] - d[o]) * (d[i] + d[o]); };
-        int64_t o2 = j;
-        const double t = secular::root_core<double>(k, j, 1.0, znorm2, &o2, diff, sum);
-        org[j] = o2;
-        tau[j] = secular::sqrt_shift(d[o2], t);
-    }
-    #pragma omp parallel for schedule(static) if (k > 256)
-    for (int64_t i = 0; i < k; ++i) {
-        const double di = d[i];
-        auto lmd = [&](int64_t j) {
-            const double dorg = d[org[j]];
-            return ((dorg - di) + tau[j]) * ((dorg + di) + tau[j]);
-        };
-        double pr = lmd(k - 1);
-        for (int64_t j = 0; j < k - 1; ++j) {
-            const double dj = (j < i) ? d[j] : d[j + 1];
-            pr *= lmd(j) / ((dj - di) * (dj + di));
-        }
-        zh[i] = std::copysign(std::sqrt(std::abs(pr)), z[i]);
-    }
-}
-
-/// host twin of bdsdc_merge_matrices (the pointers of `a` are host pointers)
-template <typename R>
-void merge_matrices_host(BdsdcMerge const& a, bool vside, int64_t ncols, R* M, int64_t ldm) {
-    const int64_t rows = a.n + (vside ? a.sqre : 0);
-    #pragma omp parallel for schedule(dynamic, 4)
-    for (int64_t jo = 0; jo < ncols; ++jo) {
-        if (jo >= a.n) {
-            for (int64_t r = 0; r < rows; ++r) M[r + jo * ldm] = R(r == a.nl ? -a.qs : (r == a.n ? a.qc : 0.0));
-            continue;
-        }
-        std::vector<double> vec(size_t(a.n), 0.0);
-        const int64_t r = a.ord[jo];
-        if (r < a.k) {
-            const double dr = a.dd[a.org[r]], tr = a.tau[r];
-            double nrm = 0;
-            for (int64_t i = 0; i < a.k; ++i) {
-                const double di = a.dd[i];
-                double u = a.zh[i] / (((di - dr) - tr) * ((di + dr) + tr));
-                if (!vside) u = (i == 0) ? -1.0 : di * u;
-                vec[a.act[i]] = u;
-                nrm += u * u;
-            }
-            nrm = 1.0 / std::sqrt(nrm);
-            for (int64_t i = 0; i < a.k; ++i) vec[a.act[i]] *= nrm;
-        } else {
-            vec[a.defl[r - a.k]] = 1.0;
-        }
-        const int64_t nrot = vside ? a.nrot_v : a.nrot_u;
-        const int64_t* rab = vside ? a.rot_ab_v : a.rot_ab_u;
-        const double* rcs = vside ? a.rot_cs_v : a.rot_cs_u;
-        for (int64_t t = nrot - 1; t >= 0; --t) {
-            const int64_t x = rab[2 * t], y = rab[2 * t + 1];
-            const double c = rcs[2 * t], sn = rcs[2 * t + 1], vx = vec[x], vy = vec[y];
-            vec[x] = c * vx - sn * vy;
-            vec[y] = sn * vx + c * vy;
-        }
-        for (int64_t row = 0; row < rows; ++row) {
-            double v;
-            if (row == a.n) v = a.qs * vec[0];
-            else {
-                v = vec[a.inv_perm[row]];
-                if (vside && row == a.nl) v *= a.qc;
-            }
-            M[row + jo * ldm] = R(v);
-        }
-    }
-}
 
 template <typename R>
 struct Solver {
@@ -149,8 +61,7 @@ struct Solver {
     std::vector<double> d, e;            // scaled bidiagonal; d becomes sigma block by block
     R *U = nullptr, *V = nullptr, *W = nullptr, *M = nullptr;
     BdsdcStats st;
-    Work<double> dvec, dscr;
-    Work<int64_t> divec;
+    DcMergeWork ws;
 
     void sync() { if (c.dev()) slate_hip_call(hipStreamSynchronize(c.stream)); }
 
@@ -258,8 +169,7 @@ struct Solver {
         std::vector<double> Ds(N), zs(N);
         for (int64_t s = 0; s < N; ++s) { Ds[s] = dn[perm[s]]; zs[s] = z[perm[s]]; }
         std::vector<char> defl_flag(N, 0);
-        std::vector<int64_t> rab_u, rab_v;
-        std::vector<double> rcs_u, rcs_v;
+        RotationList rot_u, rot_v;
         {
             const double eps = std::numeric_limits<R>::epsilon();
             double dmax = 0, zmax = 0;
@@ -271,29 +181,14 @@ struct Solver {
                 if (Ds[s] <= tol) {
                     // tiny d: z_s rotated into z_0 (V side only), a zero singular value
                     const double t = std::hypot(zs[0], zs[s]);
-                    rab_v.push_back(s); rab_v.push_back(0);
-                    rcs_v.push_back(zs[0] / t); rcs_v.push_back(-zs[s] / t);
+                    rot_v.ab.push_back(s); rot_v.ab.push_back(0);
+                    rot_v.cs.push_back(zs[0] / t); rot_v.cs.push_back(-zs[s] / t);
                     zs[0] = t; zs[s] = 0; Ds[s] = 0;
                     defl_flag[s] = 1;
                     continue;
                 }
-                if (last >= 0) {
-                    // close poles: one z rotated to zero on both sides
-                    const double t = std::hypot(zs[last], zs[s]);
-                    const double cc = zs[s] / t, sn = -zs[last] / t;
-                    if (std::abs((Ds[s] - Ds[last]) * cc * sn) <= tol) {
-                        rab_u.push_back(last); rab_u.push_back(s);
-                        rcs_u.push_back(cc); rcs_u.push_back(sn);
-                        rab_v.push_back(last); rab_v.push_back(s);
-                        rcs_v.push_back(cc); rcs_v.push_back(sn);
-                        const double dl_ = Ds[last], ds_ = Ds[s];
-                        Ds[last] = dl_ * cc * cc + ds_ * sn * sn;
-                        Ds[s] = dl_ * sn * sn + ds_ * cc * cc;
-                        zs[s] = t;
-                        zs[last] = 0;
-                        defl_flag[last] = 1;
-                    }
-                }
+                // close poles: one z rotated to zero on both sides
+                if (last >= 0 && close_pole_rotation(Ds, zs, last, s, tol, {&rot_u, &rot_v})) defl_flag[last] = 1;
                 last = s;
             }
             if (std::abs(zs[0]) <= tol) zs[0] = tol;
@@ -305,7 +200,6 @@ struct Solver {
         std::vector<double> dd(k), zz(k);
         double znorm2 = 0;
         for (int64_t i = 0; i < k; ++i) { dd[i] = Ds[act[i]]; zz[i] = zs[act[i]]; znorm2 += zz[i] * zz[i]; }
-        const int64_t nru = int64_t(rcs_u.size()) / 2, nrv = int64_t(rcs_v.size()) / 2;
         t_defl.end();
         ++st.merges;
         st.columns += N;
@@ -314,28 +208,14 @@ struct Solver {
         st.level_columns[depth] += N;
         st.level_deflated[depth] += N - k;
         // ---- secular roots, z-hat
-        // device doubles: dd k | zz k | tau k | zh k | rcs_u 2 nru | rcs_v 2 nrv
-        // device ints:    org k | act k | defl N-k | ord N | inv_perm N | rab_u 2 nru | rab_v 2 nrv
         std::vector<int64_t> org;
         std::vector<double> tau, zh;
         trace::Block t_sec("bdsdc_m_secular");
+        secular_solve<secular::SquaredPoles<double>>(c, ws, N, rot_u.count() + rot_v.count(), k, 1.0, dd, zz, znorm2,
+                                                     org, tau, zh);
         if (dev) {
-            dvec.resize(Target::Devices, size_t(4 * k + 2 * nru + 2 * nrv + 1));
-            divec.resize(Target::Devices, size_t(2 * k + 3 * N + 2 * nru + 2 * nrv + 1));
-            double* dv = dvec.data();
-            device::memcpy_async(dv, dd.data(), k * sizeof(double), c.stream);
-            device::memcpy_async(dv + k, zz.data(), k * sizeof(double), c.stream);
-            slate_amd::dev::bdsdc_secular_roots(k, dv, dv + k, znorm2, divec.data(), dv + 2 * k, c.stream);
-            slate_amd::dev::bdsdc_zhat(k, dv, dv + k, divec.data(), dv + 2 * k, dv + 3 * k, c.stream);
             ++st.launches_secular;
             ++st.launches_zhat;
-            org.resize(k);
-            tau.resize(k);
-            device::memcpy_async(org.data(), divec.data(), k * sizeof(int64_t), c.stream);
-            device::memcpy_async(tau.data(), dv + 2 * k, k * sizeof(double), c.stream);
-            sync();
-        } else {
-            secular_host(k, dd, zz, znorm2, org, tau, zh);
         }
         t_sec.end();
         // ---- singular values of the node, descending
@@ -346,59 +226,25 @@ struct Solver {
         std::iota(ord.begin(), ord.end(), int64_t(0));
         std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return sig[a] > sig[b]; });
         for (int64_t s = 0; s < N; ++s) inv_perm[perm[s]] = s;
-        BdsdcMerge mg;
-        mg.n = N; mg.k = k; mg.nl = NL; mg.sqre = sqre; mg.nrot_u = nru; mg.nrot_v = nrv;
-        mg.qc = qc; mg.qs = qs;
-        int64_t batch = 1;
-        if (dev) {
+        DcRotations drot[2];   // U side, V side
+        DcMerge mg;
+        {
             trace::Block t_m("bdsdc_m_matrix");
-            double* dv = dvec.data();
-            int64_t* iv = divec.data();
-            device::memcpy_async(iv + k, act.data(), k * sizeof(int64_t), c.stream);
-            if (N > k) device::memcpy_async(iv + 2 * k, defl.data(), (N - k) * sizeof(int64_t), c.stream);
-            device::memcpy_async(iv + k + N, ord.data(), N * sizeof(int64_t), c.stream);
-            device::memcpy_async(iv + k + 2 * N, inv_perm.data(), N * sizeof(int64_t), c.stream);
-            if (nru) {
-                device::memcpy_async(iv + k + 3 * N, rab_u.data(), 2 * nru * sizeof(int64_t), c.stream);
-                device::memcpy_async(dv + 4 * k, rcs_u.data(), 2 * nru * sizeof(double), c.stream);
-            }
-            if (nrv) {
-                device::memcpy_async(iv + k + 3 * N + 2 * nru, rab_v.data(), 2 * nrv * sizeof(int64_t), c.stream);
-                device::memcpy_async(dv + 4 * k + 2 * nru, rcs_v.data(), 2 * nrv * sizeof(double), c.stream);
-            }
-            mg.dd = dv; mg.tau = dv + 2 * k; mg.zh = dv + 3 * k;
-            mg.org = iv; mg.act = iv + k; mg.defl = iv + 2 * k; mg.ord = iv + k + N; mg.inv_perm = iv + k + 2 * N;
-            mg.rot_ab_u = iv + k + 3 * N; mg.rot_ab_v = iv + k + 3 * N + 2 * nru;
-            mg.rot_cs_u = dv + 4 * k; mg.rot_cs_v = dv + 4 * k + 2 * nru;
-            // columns in batches: scratch of batch x N doubles under a byte budget
-            batch = std::max<int64_t>(1, std::min<int64_t>(Nv, int64_t(256 << 20) / (8 * N)));
-            dscr.resize(Target::Devices, size_t(batch) * N);
-        } else {
-            mg.dd = dd.data(); mg.tau = tau.data(); mg.zh = zh.data();
-            mg.org = org.data(); mg.act = act.data(); mg.defl = defl.data(); mg.ord = ord.data();
-            mg.inv_perm = inv_perm.data();
-            mg.rot_ab_u = rab_u.data(); mg.rot_ab_v = rab_v.data();
-            mg.rot_cs_u = rcs_u.data(); mg.rot_cs_v = rcs_v.data();
+            mg = merge_layout(c, ws, N, dd, zh, tau, org, act, defl, ord, inv_perm, {&rot_u, &rot_v}, drot);
         }
-        auto build = [&](bool vside) {
+        BdsdcSide side;
+        side.nl = NL; side.sqre = sqre; side.qc = qc; side.qs = qs;
+        auto build = [&](int vside) {
             trace::Block t_m("bdsdc_m_matrix");
-            const int64_t cols = vside ? Nv : N;
-            if (dev) {
-                for (int64_t c0 = 0; c0 < cols; c0 += batch) {
-                    slate_amd::dev::bdsdc_merge_matrices<R>(mg, vside, c0, std::min(batch, cols - c0), M, ld,
-                                                            dscr.data(), c.stream);
-                    ++st.launches_matrix;
-                }
-            } else {
-                merge_matrices_host<R>(mg, vside, cols, M, ld);
-            }
+            side.vside = vside;
+            st.launches_matrix += merge_columns<R>(c, ws, mg, drot[vside], side, vside ? Nv : N, M, ld);
         };
         auto gemm_ = [&](int64_t mm, int64_t nn, int64_t kk, const R* A, const R* B, R* C) {
             if (mm > 0 && nn > 0 && kk > 0)
                 lb::gemm<R>(c, Op::NoTrans, Op::NoTrans, mm, nn, kk, R(1), A, ld, B, ld, R(0), C, ld);
         };
         // ---- U := diag(U1, 1, U2) MU
-        build(false);
+        build(0);
         {
             trace::Block t_g("bdsdc_m_gemm");
             R* Ub = U + lo + lo * ld;
@@ -407,7 +253,7 @@ struct Solver {
             lb::copy2d(c, N, N, W, ld, Ub, ld);
         }
         // ---- V := diag(V1, V2) MV
-        build(true);
+        build(1);
         {
             trace::Block t_g("bdsdc_m_gemm");
             R* Vb = V + lo + lo * ld;

@@ -13,9 +13,10 @@
 //     of n2 values;
 //   * sort, deflation (tiny z, close pairs -> Givens rotations recorded, not
 //     applied) on the host, replicated and deterministic: O(n2 log n2);
-//   * secular roots and Gu-Eisenstat z on the device (one thread per root);
+//   * secular roots (one wave per root) and Gu-Eisenstat z on the device;
 //   * the merge matrix M (Q_new = Q_old M, n2 x n2) built by every rank for
-//     its OWN local entries only (kernels/stedc.hip);
+//     its OWN local entries only -- both through dc_merge.hh, the merge
+//     shared with bdsdc (kernels/dc_merge.hip, host twins in dc_merge.cc);
 //   * Q_new = [Q1 0; 0 Q2] M as two distributed MFMA GEMMs on the halves.
 // No rank holds an n x n array on the host: per-rank host memory is O(n + nb^2).
 //
@@ -25,9 +26,9 @@
 // own rows with no communication -- on the device through the batched
 // wavefront rotation kernel of bdsqr.
 #include "internal.hh"
+#include "dc_merge.hh"
 #include "eig_sinks.hh"
 #include "slate_amd/eig_host.hh"
-#include "slate_amd/secular.hh"
 #include "../kernels/kernels.hh"
 
 #include <algorithm>
@@ -49,66 +50,6 @@ void split_tree(int64_t t0, int64_t t1, std::vector<SplitNode>& merges, std::vec
     split_tree(tm, t1, merges, cuts);
     merges.push_back({t0, tm, t1, 0.0});
     cuts.push_back(tm);
-}
-
-/// host twin of the device merge-matrix kernel (host target / tests)
-template <typename R>
-void merge_matrix_host(slate_amd::dev::StedcMerge const& m, std::vector<double> const& dd, std::vector<double> const& zh,
-                       std::vector<double> const& tau, std::vector<int64_t> const& org, std::vector<int64_t> const& act,
-                       std::vector<int64_t> const& defl, std::vector<int64_t> const& ord,
-                       std::vector<int64_t> const& inv_perm, std::vector<int64_t> const& rab,
-                       std::vector<double> const& rcs, int64_t ncols, R* M, int64_t ldm) {
-    auto l2g_ = [](int64_t l, int64_t b, int64_t procs, int64_t rel) { return ((l / b) * procs + rel) * b + l % b; };
-    #pragma omp parallel for schedule(dynamic, 4)
-    for (int64_t lc = 0; lc < ncols; ++lc) {
-        std::vector<double> vec(size_t(m.n2), 0.0);
-        const int64_t jo = l2g_(m.lc0 + lc, m.nb, m.q, m.crel) - m.col_off;
-        const int64_t r = ord[jo];
-        if (r < m.k) {
-            const double dr = dd[org[r]], tr = tau[r];
-            double nrm = 0;
-            for (int64_t i = 0; i < m.k; ++i) {
-                const double u = zh[i] / ((dd[i] - dr) - tr);
-                vec[act[i]] = u;
-                nrm += u * u;
-            }
-            nrm = 1.0 / std::sqrt(nrm);
-            for (int64_t i = 0; i < m.k; ++i) vec[act[i]] *= nrm;
-        } else {
-            vec[defl[r - m.k]] = 1.0;
-        }
-        for (int64_t t = m.nrot - 1; t >= 0; --t) {
-            const int64_t x = rab[2 * t], y = rab[2 * t + 1];
-            const double c = rcs[2 * t], sn = rcs[2 * t + 1], vx = vec[x], vy = vec[y];
-            vec[x] = c * vx - sn * vy;
-            vec[y] = sn * vx + c * vy;
-        }
-        for (int64_t lr = 0; lr < m.lrows; ++lr) {
-            const int64_t src = l2g_(m.lr0 + lr, m.mb, m.p, m.rrel) - m.row_off;
-            M[lr + lc * ldm] = R(vec[inv_perm[src]]);
-        }
-    }
-}
-
-/// secular roots + Gu-Eisenstat z on the host (same algorithm as the kernels)
-void secular_host(int64_t k, double rho, std::vector<double> const& dd, std::vector<double> const& zz,
-                  std::vector<int64_t>& org, std::vector<double>& tau, std::vector<double>& zh) {
-    double znorm2 = 0;
-    for (int64_t i = 0; i < k; ++i) znorm2 += zz[i] * zz[i];
-    org.assign(k, 0); tau.assign(k, 0.0); zh.assign(k, 0.0);
-    #pragma omp parallel for schedule(dynamic, 8) if (k > 64)
-    for (int64_t j = 0; j < k; ++j) {
-        int64_t o2 = j;
-        tau[j] = secular::root<double>(k, j, rho, dd.data(), zz.data(), znorm2, &o2);
-        org[j] = o2;
-    }
-    #pragma omp parallel for schedule(static) if (k > 256)
-    for (int64_t i = 0; i < k; ++i) {
-        auto lmd = [&](int64_t j) { return (dd[org[j]] - dd[i]) + tau[j]; };
-        double pr = lmd(k - 1) / rho;
-        for (int64_t j = 0; j < k - 1; ++j) pr *= lmd(j) / ((j < i) ? (dd[j] - dd[i]) : (dd[j + 1] - dd[i]));
-        zh[i] = std::copysign(std::sqrt(std::abs(pr)), zz[i]);
-    }
 }
 
 }  // namespace
@@ -171,8 +112,7 @@ void stedc_dist(std::vector<R>& d, std::vector<R> const& e_in, Matrix<R>& Q, Opt
     Qb.insertLocalTiles(target);
     M.insertLocalTiles(target);
     auto& st = *Q.storage();
-    Work<double> dvec, dscr;
-    Work<int64_t> divec;
+    DcMergeWork ws;
     for (auto const& nd : merges) {
         trace::Block t2("stedc_merge");
         const int64_t lo = grow_of(Q, nd.t0), mid = grow_of(Q, nd.tm), hi = grow_of(Q, nd.t1);
@@ -211,8 +151,7 @@ void stedc_dist(std::vector<R>& d, std::vector<R> const& e_in, Matrix<R>& Q, Opt
         std::vector<double> Ds(n2), zs(n2);
         for (int64_t s = 0; s < n2; ++s) { Ds[s] = double(d[lo + perm[s]]); zs[s] = z[perm[s]]; }
         std::vector<char> defl_flag(n2, 0);
-        std::vector<int64_t> rab;
-        std::vector<double> rcs;
+        RotationList rot;
         {
             trace::Block t3("stedc_m_deflate");
             const double eps = std::numeric_limits<R>::epsilon();
@@ -223,20 +162,7 @@ void stedc_dist(std::vector<R>& d, std::vector<R> const& e_in, Matrix<R>& Q, Opt
             int64_t last = -1;
             for (int64_t j = 0; j < n2; ++j) {
                 if (defl_flag[j]) continue;
-                if (last >= 0) {
-                    const double t = std::hypot(zs[last], zs[j]);
-                    const double cc = zs[j] / t, sn = -zs[last] / t;
-                    if (std::abs((Ds[j] - Ds[last]) * cc * sn) <= tol) {
-                        rab.push_back(last); rab.push_back(j);
-                        rcs.push_back(cc); rcs.push_back(sn);
-                        const double dlst = Ds[last], dj = Ds[j];
-                        Ds[last] = dlst * cc * cc + dj * sn * sn;
-                        Ds[j] = dlst * sn * sn + dj * cc * cc;
-                        zs[j] = t;
-                        zs[last] = 0;
-                        defl_flag[last] = 1;
-                    }
-                }
+                if (last >= 0 && close_pole_rotation(Ds, zs, last, j, tol, {&rot})) defl_flag[last] = 1;
                 last = j;
             }
         }
@@ -246,32 +172,15 @@ void stedc_dist(std::vector<R>& d, std::vector<R> const& e_in, Matrix<R>& Q, Opt
         const int64_t k = int64_t(act.size());
         std::vector<double> dd(k), zz(k);
         for (int64_t i = 0; i < k; ++i) { dd[i] = Ds[act[i]]; zz[i] = zs[act[i]]; }
+        // a loop of its own: fused with the gather above, g++ fuses the products into the sum and the last
+        // root, with it the results pinned by test_stedc_bitwise_unchanged, move by an ulp
+        double znorm2 = 0;
+        for (int64_t i = 0; i < k; ++i) znorm2 += zz[i] * zz[i];
         // ---- secular roots (device or host), eigenvalues, output order
         std::vector<int64_t> org;
         std::vector<double> tau, zh;
-        const bool dev = c.dev();
-        // device vector block: dd k | zz k | tau k | zh k | rcs 2 nrot ; ints: org k | act k | defl n2-k | ord n2 | inv n2 | rab 2 nrot
-        const int64_t nrot = int64_t(rcs.size()) / 2;
         trace::Block t3s("stedc_m_secular");
-        if (dev) {
-            dvec.resize(Target::Devices, size_t(4 * k + 2 * nrot + 1));
-            divec.resize(Target::Devices, size_t(2 * k + 3 * n2 + 2 * nrot + 1));
-            double znorm2 = 0;
-            for (int64_t i = 0; i < k; ++i) znorm2 += zz[i] * zz[i];
-            device::memcpy_async(dvec.data(), dd.data(), k * sizeof(double), c.stream);
-            device::memcpy_async(dvec.data() + k, zz.data(), k * sizeof(double), c.stream);
-            slate_amd::dev::secular_roots(k, rho, dvec.data(), dvec.data() + k, znorm2, divec.data(), dvec.data() + 2 * k,
-                                          c.stream);
-            slate_amd::dev::gu_eisenstat(k, rho, dvec.data(), dvec.data() + k, divec.data(), dvec.data() + 2 * k,
-                                         dvec.data() + 3 * k, c.stream);
-            org.resize(k);
-            tau.resize(k);
-            device::memcpy_async(org.data(), divec.data(), k * sizeof(int64_t), c.stream);
-            device::memcpy_async(tau.data(), dvec.data() + 2 * k, k * sizeof(double), c.stream);
-            slate_hip_call(hipStreamSynchronize(c.stream));
-        } else {
-            secular_host(k, rho, dd, zz, org, tau, zh);
-        }
+        secular_solve<secular::LinearPoles<double>>(c, ws, n2, rot.count(), k, rho, dd, zz, znorm2, org, tau, zh);
         t3s.end();
         std::vector<double> lam(n2);
         for (int64_t r = 0; r < k; ++r) lam[r] = dd[org[r]] + tau[r];
@@ -284,33 +193,14 @@ void stedc_dist(std::vector<R>& d, std::vector<R> const& e_in, Matrix<R>& Q, Opt
         trace::Block t3m("stedc_m_matrix");
         Matrix<R> Mb = M.sub(nd.t0, nd.t1 - 1, nd.t0, nd.t1 - 1);
         LocalBlock<R> lm = Mb.local(loc, true);
-        slate_amd::dev::StedcMerge mg;
-        mg.n2 = n2; mg.k = k; mg.nrot = nrot;
-        mg.lrows = lm.m; mg.mb = st.mb; mg.p = g.p(); mg.rrel = st.rrel(); mg.row_off = lo;
-        mg.nb = st.nb; mg.q = g.q(); mg.crel = st.crel(); mg.col_off = lo;
-        mg.lr0 = Mb.lrow_begin(); mg.lc0 = Mb.lcol_begin();
-        if (dev) {
-            int64_t* iv = divec.data();
-            device::memcpy_async(iv + k, act.data(), k * sizeof(int64_t), c.stream);
-            if (n2 > k) device::memcpy_async(iv + 2 * k, defl.data(), (n2 - k) * sizeof(int64_t), c.stream);
-            device::memcpy_async(iv + k + n2, ord.data(), n2 * sizeof(int64_t), c.stream);
-            device::memcpy_async(iv + k + 2 * n2, inv_perm.data(), n2 * sizeof(int64_t), c.stream);
-            if (nrot) {
-                device::memcpy_async(iv + k + 3 * n2, rab.data(), 2 * nrot * sizeof(int64_t), c.stream);
-                device::memcpy_async(dvec.data() + 4 * k, rcs.data(), 2 * nrot * sizeof(double), c.stream);
-            }
-            mg.dd = dvec.data(); mg.zh = dvec.data() + 3 * k; mg.tau = dvec.data() + 2 * k;
-            mg.org = iv; mg.act = iv + k; mg.defl = iv + 2 * k; mg.ord = iv + k + n2; mg.inv_perm = iv + k + 2 * n2;
-            mg.rot_ab = iv + k + 3 * n2; mg.rot_cs = dvec.data() + 4 * k;
-            // columns in batches: scratch of batch x n2 reals
-            const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(lm.n, int64_t(256 << 20) / (8 * std::max<int64_t>(n2, 1))));
-            dscr.resize(Target::Devices, size_t(batch) * n2);
-            for (int64_t c0 = 0; c0 < lm.n; c0 += batch)
-                slate_amd::dev::merge_matrix<R>(mg, c0, std::min(batch, lm.n - c0), lm.ptr, lm.ld, dscr.data(), c.stream);
-            slate_hip_call(hipStreamSynchronize(c.stream));
-        } else {
-            merge_matrix_host<R>(mg, dd, zh, tau, org, act, defl, ord, inv_perm, rab, rcs, lm.n, lm.ptr, lm.ld);
-        }
+        StedcSide side;
+        side.lrows = lm.m; side.mb = st.mb; side.p = g.p(); side.rrel = st.rrel(); side.row_off = lo;
+        side.nb = st.nb; side.q = g.q(); side.crel = st.crel(); side.col_off = lo;
+        side.lr0 = Mb.lrow_begin(); side.lc0 = Mb.lcol_begin();
+        DcRotations drot;
+        const DcMerge mg = merge_layout(c, ws, n2, dd, zh, tau, org, act, defl, ord, inv_perm, {&rot}, &drot);
+        merge_columns<R>(c, ws, mg, drot, side, lm.n, lm.ptr, lm.ld);
+        if (c.dev()) slate_hip_call(hipStreamSynchronize(c.stream));
         t3m.end();
         // ---- Q_new = [Q1 0; 0 Q2] M  (two GEMMs on the halves), back into Q
         {

@@ -1,7 +1,8 @@
 """Bidiagonal divide and conquer (csrc/src/bdsdc.cc, host target): bdsdc
 against numpy on every size class and on the hard spectra, the sqre = 1 leaf,
 svd with method_svd="dc" against numpy and the QR path, a 2 x 2 grid, the
-native tester, and bit-for-bit stedc results after the secular.hh refactor."""
+native tester, and bit-for-bit stedc and bdsdc results across the secular.hh
+and dc_merge refactors."""
 import hashlib
 import os
 import socket
@@ -233,3 +234,45 @@ def test_stedc_bitwise_unchanged(kind):
     assert np.array_equal(w2, g("w_matrix"))
     assert np.array_equal(q[::25], g("q_rows"))
     assert np.array_equal(_sha(q), g("q_sha256"))
+
+
+# ---- the host bdsdc path after the merge moved to dc_merge: bit for bit
+BDSDC_PINNED = {"random": ("random", 600), "cluster": ("cluster", 600), "zerodiag": ("zerodiag", 600),
+                "tiny": ("tiny", 600), "graded": ("graded", 257), "leaf8": ("random", 100),
+                "float32": ("random", 130)}
+
+
+def _bdsdc_pinned(case):
+    """(sv, u, vt) of one pinned case: s.bdsdc, with SLATE_BDSDC_LEAF=8 for
+    leaf8, and float32 identities through bdsdc_matrix (nb = 32) for float32."""
+    kind, n = BDSDC_PINNED[case]
+    d, e, _ = bidiagonal(kind, n)
+    if case == "float32":
+        U, VT = (s.from_numpy(np.eye(n, dtype=np.float32), nb=32) for _ in range(2))
+        sv = s.bdsdc_matrix(s.Job.Vec, s.Job.Vec, d.astype(np.float32), e.astype(np.float32), U, VT)
+        return np.asarray(sv), s.to_numpy(U), s.to_numpy(VT)
+    old = os.environ.get("SLATE_BDSDC_LEAF")
+    if case == "leaf8":
+        os.environ["SLATE_BDSDC_LEAF"] = "8"
+    try:
+        sv, u, vt = s.bdsdc(d, e)
+    finally:
+        if case == "leaf8":
+            os.environ.pop("SLATE_BDSDC_LEAF")
+            if old is not None:
+                os.environ["SLATE_BDSDC_LEAF"] = old
+    return np.asarray(sv), np.asarray(u), np.asarray(vt)
+
+
+@pytest.mark.parametrize("case", list(BDSDC_PINNED))
+def test_bdsdc_bitwise_unchanged(case):
+    """Singular values (whole), and U and VT (SHA-256 and every 25th row) of
+    the host-target bdsdc, captured before the merge of stedc_dist and bdsdc
+    became one (dc_merge.cc).  The outputs do not depend on the thread count."""
+    g = lambda name: np.load(os.path.join(GOLDEN, f"bdsdc_{case}_{name}.npy"))  # noqa: E731
+    sv, u, vt = _bdsdc_pinned(case)
+    assert np.array_equal(sv, g("sv"))
+    assert np.array_equal(u[::25], g("u_rows"))
+    assert np.array_equal(vt[::25], g("vt_rows"))
+    assert np.array_equal(_sha(u), g("u_sha256"))
+    assert np.array_equal(_sha(vt), g("vt_sha256"))

@@ -1,5 +1,5 @@
 """Bidiagonal divide and conquer on the device target: the three kernels of
-csrc/kernels/bdsdc.hip (secular roots, z-hat, merge matrices) with the MFMA
+csrc/kernels/dc_merge.hip (secular roots, z-hat, merge columns) with the MFMA
 GEMM merges, against numpy with the bounds of bdsdc_cases.check, and svd with
 method_svd="dc" on the device."""
 import numpy as np
