@@ -118,7 +118,7 @@ def interface(ret, name, args):
 
 
 def options(text):
-    return re.findall(r"(slate_(?:Option|GemmPrecision|MethodSVD|MethodHetrd)_\w+)\s*=\s*(\d+)", text)
+    return re.findall(r"(slate_(?:Option|GemmPrecision|MethodSVD|MethodHetrd|MethodGebrd)_\w+)\s*=\s*(\d+)", text)
 
 
 def main():

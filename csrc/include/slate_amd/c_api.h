@@ -31,8 +31,13 @@ enum {
     slate_Option_MethodCholQR = 60, slate_Option_MethodEig = 61, slate_Option_MethodGels = 62,
     slate_Option_MethodGemm = 63, slate_Option_MethodHemm = 64, slate_Option_MethodLU = 65,
     slate_Option_MethodTrsm = 66, slate_Option_MethodSVD = 67,
-    slate_Option_MethodHetrd = 68
+    slate_Option_MethodHetrd = 68, slate_Option_MethodGebrd = 69
 };
+
+/* ivalue of slate_Option_MethodGebrd (slate::MethodGebrd): bidiagonal
+ * reduction of slate_svd*, two stages (default) or the one-stage gebrd (real
+ * types, one process) */
+enum { slate_MethodGebrd_TwoStage = 50, slate_MethodGebrd_OneStage = 49 };
 
 /* ivalue of slate_Option_MethodHetrd (slate::MethodHetrd): tridiagonal
  * reduction of slate_hermitian_eig*, two stages (default) or the one-stage

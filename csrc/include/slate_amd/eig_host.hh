@@ -145,5 +145,13 @@ int64_t steqr_core(int64_t n, R* d, R* e, RotSink<R>* sink);
 template <typename R>
 void hetrd(int64_t n, R* A, int64_t lda, R* d, R* e, R* tau, int64_t nb);
 
+/// One-stage bidiagonal reduction of a real m x n A, m >= n (LAPACK gebrd,
+/// labrd panels of nb columns): A = Q B P^T, B upper bidiagonal with diagonal
+/// d (n) and superdiagonal e (n - 1), Q = H_0 .. H_{n-1}, H_i = I - tauq_i u_i
+/// u_i^T with u_i in A(i:m, i), P = G_0 .. G_{n-2}, G_i = I - taup_i v_i v_i^T
+/// with v_i in A(i, i+1:n); the unit entries are stored.
+template <typename R>
+void gebrd(int64_t m, int64_t n, R* A, int64_t lda, R* d, R* e, R* tauq, R* taup, int64_t nb);
+
 }  // namespace host
 }  // namespace slate

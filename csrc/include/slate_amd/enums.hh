@@ -52,6 +52,12 @@ enum class MethodSVD : char { QR = 'Q', DC = 'D' };
 /// hetrd (sytrd panels, a symv per column on the device).  Not in the reference.
 enum class MethodHetrd : char { TwoStage = '2', OneStage = '1' };
 
+/// Bidiagonal reduction of svd / gesvd / svd_vals: two stages (ge2tb on the
+/// device, the bulge chase tb2bd on the host; default) or the one-stage gebrd
+/// (labrd panels, two matrix-vector products per column on the device).  Not
+/// in the reference.
+enum class MethodGebrd : char { TwoStage = '2', OneStage = '1' };
+
 /// Arithmetic of the large device fp32 products (trailing updates) of a
 /// routine: the fp32 MFMA kernels, or the split-operand bf16 MFMA kernel with
 /// 1, 3 or 6 plane products per K-step (gemm_bf16s.hip).  Not in the reference.
@@ -98,6 +104,8 @@ enum class Option : char {
     MethodSVD,
     /// MethodHetrd of heev / syev / hegv / sygv.  Default TwoStage.  Not in the reference.
     MethodHetrd,
+    /// MethodGebrd of svd / gesvd / svd_vals.  Default TwoStage.  Not in the reference.
+    MethodGebrd,
 };
 
 const int HostNum    = -1;

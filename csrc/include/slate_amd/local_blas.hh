@@ -139,6 +139,12 @@ void trmm(Ctx const& c, Side side, Uplo uplo, Op op, Diag diag, int64_t m, int64
 template <typename R>
 void symv_lower(Ctx const& c, int64_t m, R const* A, int64_t lda, R const* x, R* y);
 
+/// y = A x (Op::NoTrans, y of mr) or y = A^T x (Op::Trans, y of nc) for the
+/// mr x nc block at A, device only: the product kernels of kernels/gebrd.hip,
+/// which load nothing outside the block; no atomics, bitwise reproducible.
+template <typename R>
+void gemv_block(Ctx const& c, Op op, int64_t mr, int64_t nc, R const* A, int64_t lda, R const* x, R* y);
+
 // ---------------- LAPACK-style
 /// Cholesky of an n x n block; info (device int on Devices, host int on Host)
 /// receives info_offset + failing column if not already set.

@@ -398,6 +398,41 @@ struct HetrdStats {
 };
 HetrdStats hetrd_stats();
 
+/// Which factor of the bidiagonal reduction unmbr_gebrd applies (LAPACK ormbr's vect).
+enum class Vect : char { Q = 'Q', P = 'P' };
+/// One-stage bidiagonal reduction (src/gebrd.cc; LAPACK gebrd): A = Q B P^T
+/// with B upper bidiagonal, diagonal D (n) and superdiagonal E (n - 1).  Real
+/// types, m >= n, a matrix of one process on one device or the host; anything
+/// else throws NotImplemented.  The left reflectors stay in A below the
+/// diagonal, the right ones to the right of the superdiagonal, each with its
+/// unit entry stored.  TQ[0] / TP[0] hold the 64 x 64 block-reflector factor
+/// of every panel of 64 columns (panel p at column 64 p), TQ[1] / TP[1] the
+/// scalars tauq / taup.  The entries of A are assumed to be such that their
+/// squares neither overflow nor underflow (svd scales first).
+template <typename T>
+void gebrd(Matrix<T>& A, std::vector<real_type<T>>& D, std::vector<real_type<T>>& E, TriangularFactors<T>& TQ,
+           TriangularFactors<T>& TP, Options const& opts = {});
+/// C := op(F) C (Side::Left) or C op(F) (Side::Right), F = Q = H_0 .. H_{n-1}
+/// (Vect::Q, order m, T = TQ) or F = P = G_0 .. G_{n-2} (Vect::P, order n,
+/// T = TP) from gebrd(A, ...): LAPACK ormbr, one larfb per panel.
+template <typename T>
+void unmbr_gebrd(Vect vect, Side side, Op op, Matrix<T>& A, TriangularFactors<T>& T_, Matrix<T>& C,
+                 Options const& opts = {});
+/// Counters of the last one-stage bidiagonal reduction of this process (gebrd,
+/// or svd with MethodGebrd::OneStage): reduced columns, panels, launches of the
+/// seven column kernels (zero on the host target) and host synchronisations
+/// inside the reduction.  With SLATE_GEBRD_PROFILE=1 in the environment the
+/// device reduction also records events between its kernels and reports the
+/// device milliseconds of pass 1 (A^T u), pass 2 (A v), the other column
+/// kernels (panel), the trailing GEMMs and the T factors; zero otherwise.
+struct GebrdStats {
+    int64_t columns = 0, panels = 0, host_syncs = 0;
+    int64_t launches_column = 0, launches_larfg_u = 0, launches_pass1 = 0, launches_finish_y = 0,
+            launches_larfg_v = 0, launches_pass2 = 0, launches_finish_x = 0;
+    double ms_pass1 = 0, ms_pass2 = 0, ms_panel = 0, ms_gemm = 0, ms_larft = 0;
+};
+GebrdStats gebrd_stats();
+
 //------------------------------------------------------------------------------
 // Real-symmetric aliases (real types only) and compatibility names.
 template <typename T>

@@ -53,6 +53,7 @@ public:
     OptionValue(MethodEig m) : i_(int64_t(m)), d_(0) {}
     OptionValue(MethodSVD m) : i_(int64_t(m)), d_(0) {}
     OptionValue(MethodHetrd m) : i_(int64_t(m)), d_(0) {}
+    OptionValue(MethodGebrd m) : i_(int64_t(m)), d_(0) {}
     OptionValue(GemmPrecision g) : i_(int64_t(g)), d_(0) {}
     int64_t i_;
     double d_;

@@ -221,6 +221,55 @@ void hetrd_symv(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, Hetrd
 template <typename R>
 void hetrd_correct(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s);
 
+// ---- one-stage bidiagonal reduction (gebrd.hip), float and double
+/// y = A^T x (gemv_t_block, y of nc) and y = A x (gemv_n_block, y of mr) for
+/// the mr x nc block at A: nothing outside the block is loaded.  No atomics:
+/// partials in work (gemv_t_block_workspace / gemv_n_block_workspace
+/// elements), summed in a fixed order.
+template <typename R>
+void gemv_t_block(int64_t mr, int64_t nc, const R* A, int64_t lda, const R* x, R* y, R* work, hipStream_t s);
+template <typename R>
+void gemv_n_block(int64_t mr, int64_t nc, const R* A, int64_t lda, const R* x, R* y, R* work, hipStream_t s);
+int64_t gemv_t_block_workspace(int64_t mr, int64_t nc);
+int64_t gemv_n_block_workspace(int64_t mr, int64_t nc);
+/// row tiles per wave of the split of an mr x nc block, and its chunks of row tiles
+int gemv_block_tpw(int64_t mr, int64_t nc);
+int64_t gemv_block_chunks(int64_t mr, int tpw);
+/// device vectors of a reduction of an m x n matrix with panels of 64 columns
+template <typename R>
+struct GebrdWork {
+    R *X = nullptr, *Y = nullptr;            // m x 64 and n x 64
+    int64_t ldx = 0, ldy = 0;
+    R *u = nullptr, *v = nullptr;            // m and n: the current reflectors
+    R *scal = nullptr;                       // 2: alpha of the current column, of the current row
+    R *ssq = nullptr, *ssq2 = nullptr;       // ceil(m / 64) and ceil(n / 64): partial sums of squares
+    R *pdots = nullptr;                      // ceil(max(m, n) / 256) x 128: partials of the small dots
+    R *colpart = nullptr, *rowpart = nullptr;   // product partials: (m / 256 + 2) n and (n / 16 + 2) m
+    R *d = nullptr, *e = nullptr, *tauq = nullptr, *taup = nullptr;   // n each
+};
+/// the seven launches of column i of the panel that starts at j0 (see gebrd.hip)
+template <typename R>
+void gebrd_column(int64_t m, int64_t i, int64_t j0, R* A, int64_t lda, GebrdWork<R> const& wk, hipStream_t s);
+template <typename R>
+void gebrd_larfg_u(int64_t m, int64_t i, R* A, int64_t lda, GebrdWork<R> const& wk, hipStream_t s);
+template <typename R>
+void gebrd_pass1(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, GebrdWork<R> const& wk,
+                 hipStream_t s);
+template <typename R>
+void gebrd_finish_y(int64_t m, int64_t n, int64_t i, int64_t j0, R* A, int64_t lda, GebrdWork<R> const& wk,
+                    hipStream_t s);
+template <typename R>
+void gebrd_larfg_v(int64_t n, int64_t i, R* A, int64_t lda, GebrdWork<R> const& wk, hipStream_t s);
+template <typename R>
+void gebrd_pass2(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, GebrdWork<R> const& wk,
+                 hipStream_t s);
+template <typename R>
+void gebrd_finish_x(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, GebrdWork<R> const& wk,
+                    hipStream_t s);
+/// out (nv x kb, unit lower trapezoid) = the transposed row block Arow (kb x nv) of right reflectors
+template <typename R>
+void gebrd_form_vt(int64_t nv, int kb, const R* Arow, int64_t lda, R* out, int64_t ldo, hipStream_t s);
+
 // ---- eigensolver back-transform (eig.hip)
 /// G (k x k Gram V^H V) -> T^{-1} = striu(G) + diag(1 / tau) in place.
 /// Stage-2 back-transform (hb2st_apply.hip), fp64.  ng groups of 64

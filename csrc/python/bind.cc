@@ -185,6 +185,13 @@ Options to_options(py::dict d) {
             else if (mname == "one_stage") o[Option::MethodHetrd] = MethodHetrd::OneStage;
             else throw Exception("method_hetrd: \"two_stage\" or \"one_stage\", not " + mname);
         }
+        else if (k == "method_gebrd") {
+            std::string mname = v.cast<std::string>();
+            for (auto& ch : mname) ch = char(std::tolower((unsigned char)ch));
+            if (mname == "two_stage") o[Option::MethodGebrd] = MethodGebrd::TwoStage;
+            else if (mname == "one_stage") o[Option::MethodGebrd] = MethodGebrd::OneStage;
+            else throw Exception("method_gebrd: \"two_stage\" or \"one_stage\", not " + mname);
+        }
         else if (k == "print_verbose") o[Option::PrintVerbose] = v.cast<int64_t>();
         else if (k == "print_edge_items") o[Option::PrintEdgeItems] = v.cast<int64_t>();
         else if (k == "print_width") o[Option::PrintWidth] = v.cast<int64_t>();
@@ -434,6 +441,9 @@ PYBIND11_MODULE(_slate, m) {
     py::enum_<MethodSVD>(m, "MethodSVD").value("QR", MethodSVD::QR).value("DC", MethodSVD::DC);
     py::enum_<MethodHetrd>(m, "MethodHetrd").value("TwoStage", MethodHetrd::TwoStage)
         .value("OneStage", MethodHetrd::OneStage);
+    py::enum_<MethodGebrd>(m, "MethodGebrd").value("TwoStage", MethodGebrd::TwoStage)
+        .value("OneStage", MethodGebrd::OneStage);
+    py::enum_<Vect>(m, "Vect").value("Q", Vect::Q).value("P", Vect::P);
     py::enum_<Job>(m, "Job").value("NoVec", Job::NoVec).value("Vec", Job::Vec);
 
     py::class_<Comm, std::shared_ptr<Comm>>(m, "Comm")
@@ -589,6 +599,49 @@ PYBIND11_MODULE(_slate, m) {
         for (int k = 0; k < std::max(repeat, 1); ++k) {
             if (type == "d") lb::symv_lower<double>(c, mm, (double const*)A, lda, (double const*)x, (double*)y);
             else lb::symv_lower<float>(c, mm, (float const*)A, lda, (float const*)x, (float*)y);
+        }
+        slate_hip_call(hipStreamSynchronize(c.stream));
+    });
+    m.def("gebrd_stats", []() {
+        const GebrdStats st = gebrd_stats();
+        py::dict r;
+        r["columns"] = st.columns;
+        r["panels"] = st.panels;
+        r["host_syncs"] = st.host_syncs;
+        r["launches_column"] = st.launches_column;
+        r["launches_larfg_u"] = st.launches_larfg_u;
+        r["launches_pass1"] = st.launches_pass1;
+        r["launches_finish_y"] = st.launches_finish_y;
+        r["launches_larfg_v"] = st.launches_larfg_v;
+        r["launches_pass2"] = st.launches_pass2;
+        r["launches_finish_x"] = st.launches_finish_x;
+        r["ms_pass1"] = st.ms_pass1;
+        r["ms_pass2"] = st.ms_pass2;
+        r["ms_panel"] = st.ms_panel;
+        r["ms_gemm"] = st.ms_gemm;
+        r["ms_larft"] = st.ms_larft;
+        return r;
+    });
+    // y = A^T x (trans) or A x over the mr x nc block at A (device pointers); use_lb: through
+    // lb::gemv instead of the block kernels (the yardstick)
+    // (repeat: the product is enqueued that many times before the one synchronisation, for timing)
+    m.def("lb_gemv_block", [](std::string type, bool trans, int64_t mr, int64_t nc, uintptr_t A, int64_t lda,
+                              uintptr_t x, uintptr_t y, int repeat, bool use_lb) {
+        if (type != "d" && type != "s") throw Exception("gemv_block: float32 or float64");
+        py::gil_scoped_release r;
+        auto c = lb::Ctx::device(ops_queue());
+        const Op op = trans ? Op::Trans : Op::NoTrans;
+        const int64_t my = trans ? nc : mr, ky = trans ? mr : nc;
+        for (int k = 0; k < std::max(repeat, 1); ++k) {
+            if (type == "d") {
+                if (use_lb) lb::gemv<double>(c, op, my, ky, 1, 1.0, (double const*)A, lda, (double const*)x, ky, 0.0,
+                                             (double*)y, my);
+                else lb::gemv_block<double>(c, op, mr, nc, (double const*)A, lda, (double const*)x, (double*)y);
+            } else {
+                if (use_lb) lb::gemv<float>(c, op, my, ky, 1, 1.0f, (float const*)A, lda, (float const*)x, ky, 0.0f,
+                                            (float*)y, my);
+                else lb::gemv_block<float>(c, op, mr, nc, (float const*)A, lda, (float const*)x, (float*)y);
+            }
         }
         slate_hip_call(hipStreamSynchronize(c.stream));
     });

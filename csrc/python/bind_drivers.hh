@@ -342,7 +342,13 @@ void bind_drivers(py::module_& m, std::string const& s) {
         return py::make_tuple(D, E, Tf); });
     DEF("unmtr_hetrd", [](Side sd, Op op_, HermitianMatrix<T>& A, TriangularFactors<T> Tf, Matrix<T>& C, py::dict o) {
         Options op = to_options(o); py::gil_scoped_release r; unmtr_hetrd(sd, op_, A, Tf, C, op); });
-    DEF("gels_cholqr", [](Matrix<T>& A, Matrix<T>& Rm, Matrix<T>& BX, py::dict o) {
+    DEF("gebrd", [](Matrix<T>& A, py::dict o) {
+        Options op = to_options(o); std::vector<R> D, E; TriangularFactors<T> TQ, TP;
+        { py::gil_scoped_release r; gebrd(A, D, E, TQ, TP, op); }
+        return py::make_tuple(D, E, TQ, TP); });
+    DEF("unmbr_gebrd", [](Vect vt, Side sd, Op op_, Matrix<T>& A, TriangularFactors<T> Tf, Matrix<T>& C, py::dict o) {
+        Options op = to_options(o); py::gil_scoped_release r; unmbr_gebrd(vt, sd, op_, A, Tf, C, op); });
+    DEF("gels_cholqr",[](Matrix<T>& A, Matrix<T>& Rm, Matrix<T>& BX, py::dict o) {
         Options op = to_options(o); py::gil_scoped_release r; gels_cholqr(A, Rm, BX, op); });
     DEF("gels_qr", [](Matrix<T>& A, Matrix<T>& BX, py::dict o) {
         Options op = to_options(o); TriangularFactors<T> Tf;

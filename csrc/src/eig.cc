@@ -1059,6 +1059,16 @@ void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Ma
 template <typename T>
 void svd(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Matrix<T>& VT, Options const& opts) {
     {
+        const int64_t mg = get_option<int64_t>(opts, Option::MethodGebrd, int64_t(MethodGebrd::TwoStage));
+        slate_error_if_msg(mg != int64_t(MethodGebrd::TwoStage) && mg != int64_t(MethodGebrd::OneStage),
+                           "svd: Option::MethodGebrd is neither MethodGebrd::TwoStage nor MethodGebrd::OneStage");
+        if (mg == int64_t(MethodGebrd::OneStage)) {
+            internal::gebrd_check_operand<T>(A, "svd", "A");
+            if (wanted(U)) internal::gebrd_check_operand<T>(U, "svd", "U");
+            if (wanted(VT)) internal::gebrd_check_operand<T>(VT, "svd", "VT");
+        }
+    }
+    {
         bool ran = internal::spread<T>(opts, {{&A, true}, {&U, true}, {&VT, true}}, [&](std::vector<Matrix<T>>& M,
                                                                                           int r) {
             std::vector<real_type<T>> S;
@@ -1143,6 +1153,99 @@ void svd(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Matrix<T>
     rescale_values(Sigma, anorm, alpha);
 }
 
+namespace {
+
+/// svd_square with MethodGebrd::OneStage, real types, a grid of one process:
+/// gebrd on a working copy's local block, the bidiagonal stage that
+/// Option::MethodSVD selects on (d, e), then U = Q [U2; 0] and VT = V2^T P^T,
+/// one larfb per panel each.  Values only: bdsqr_core on (d, e), no factors.
+template <typename R>
+void svd_one_stage(Matrix<R>& A, std::vector<R>& Sigma, Matrix<R>& U, Matrix<R>& VT, Options const& opts) {
+    const Target target = resolve_target(opts);
+    const Loc loc = loc_of(target);
+    const int64_t m = A.m(), n = A.n(), nb = A.nb();
+    auto gA = A.grid();
+    lb::Ctx c = target == Target::Devices ? lb::Ctx::device(0) : lb::Ctx::host();
+    Matrix<R> W(m, n, nb, nb, gA);
+    W.insertLocalTiles(target);
+    slate::copy<R, R>(A, W, opts);
+    LocalBlock<R> lw = W.local(loc, true);
+    slate_error_if_msg(lw.m != m || lw.n != n, "svd: one-stage reduction needs the whole matrix in one local block");
+    Work<R> tauq(target, size_t(n)), taup(target, size_t(n));
+    Work<R> TQ(target, size_t(internal::kGebrdPanel) * n), TP(target, size_t(internal::kGebrdPanel) * n);
+    std::vector<R> d, e;
+    {
+        trace::Block t2("gebrd");
+        internal::gebrd_local<R>(c, m, n, lw.ptr, lw.ld, d, e, tauq.data(), taup.data(), TQ.data(), TP.data());
+    }
+    const bool wu = wanted(U), wv = wanted(VT);
+    if (!wu && !wv) {
+        trace::Block t2("bdsqr");
+        host::bdsqr_core<R>(n, d.data(), e.data(), nullptr);
+        Sigma = d;
+        return;
+    }
+    const int64_t msvd = get_option<int64_t>(opts, Option::MethodSVD, int64_t(MethodSVD::QR));
+    slate_error_if_msg(msvd != int64_t(MethodSVD::QR) && msvd != int64_t(MethodSVD::DC),
+                       "svd: Option::MethodSVD is neither MethodSVD::QR nor MethodSVD::DC");
+    // U2 and V2 (B = U2 diag(d) V2^T) as whole local n x n blocks
+    GridPtr gr = col_grid(gA);
+    Matrix<R> U2(n, n, nb, n, gr), V2(n, n, nb, n, gr);
+    U2.insertLocalTiles(target);
+    V2.insertLocalTiles(target);
+    if (msvd == int64_t(MethodSVD::DC)) {
+        trace::Block t2("bdsdc");
+        Work<R> UB(target, size_t(n) * n), VB(target, size_t(n) * n);
+        internal::bdsdc_local<R>(c, d, e, UB.data(), VB.data(), n);
+        internal::bdsdc_place<R>(c, U2, UB.data(), n, false, {});
+        internal::bdsdc_place<R>(c, V2, VB.data(), n, false, {});
+    } else {
+        trace::Block t2("bdsqr");
+        const std::vector<R> ones(n, R(1));
+        set_diag_rows(U2, ones, target);
+        set_diag_rows(V2, ones, target);
+        LocalBlock<R> lu = U2.local(loc, true), lv = V2.local(loc, true);
+        RowRotSink<R> sink(c, n);
+        sink.U = wu ? lu.ptr : nullptr; sink.ldu = lu.ld; sink.urows = lu.m;
+        sink.V = wv ? lv.ptr : nullptr; sink.ldv = lv.ld; sink.vrows = lv.m;
+        host::bdsqr_core<R>(n, d.data(), e.data(), &sink);
+        sink.finish();
+    }
+    Sigma = d;
+    if (wu) {
+        // U = Q [U2; 0]
+        trace::Block t2("unmbr_gebrd");
+        Matrix<R> Uw(m, n, nb, nb, gA);
+        Uw.insertLocalTiles(target);
+        if (m > n) set(R(0), R(0), Uw, opts);
+        {
+            Matrix<R> Ut = Uw.slice(0, n - 1, 0, n - 1);
+            slate::copy<R, R>(U2, Ut, opts);
+        }
+        U2 = Matrix<R>();
+        LocalBlock<R> lu = Uw.local(loc, true);
+        internal::unmbr_gebrd_local<R>(c, Vect::Q, Side::Left, Op::NoTrans, m, n, lw.ptr, lw.ld, TQ.data(), m, n, lu.ptr,
+                                       lu.ld);
+        if (c.dev()) slate_hip_call(hipStreamSynchronize(c.stream));
+        slate::copy<R, R>(Uw, U, opts);
+    }
+    if (wv) {
+        // VT = V2^T P^T
+        trace::Block t2("unmbr_gebrd");
+        Matrix<R> Vw(n, n, nb, nb, gA);
+        Vw.insertLocalTiles(target);
+        slate::copy<R, R>(transpose(V2), Vw, opts);
+        V2 = Matrix<R>();
+        LocalBlock<R> lv = Vw.local(loc, true);
+        internal::unmbr_gebrd_local<R>(c, Vect::P, Side::Right, Op::Trans, m, n, lw.ptr, lw.ld, TP.data(), n, n, lv.ptr,
+                                       lv.ld);
+        if (c.dev()) slate_hip_call(hipStreamSynchronize(c.stream));
+        slate::copy<R, R>(Vw, VT, opts);
+    }
+}
+
+}  // namespace
+
 /// Three-stage SVD of an m x n matrix with n <= m <= 5/3 n (no pre-reduction).
 template <typename T>
 void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Matrix<T>& VT, Options const& opts) {
@@ -1150,6 +1253,11 @@ void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Ma
     Target target = resolve_target(opts);
     const int64_t m = A.m(), n = A.n();
     slate_assert(m >= n);
+    if (get_option<int64_t>(opts, Option::MethodGebrd, int64_t(MethodGebrd::TwoStage)) ==
+        int64_t(MethodGebrd::OneStage)) {
+        if constexpr (!is_complex_v<T>) svd_one_stage(A, Sigma, U, VT, opts);
+        return;
+    }
     // stage 1 on kd-wide tiles (see heev)
     const int64_t kd = std::min<int64_t>(A.nb(), eig_band_width());
     auto gA = A.grid();

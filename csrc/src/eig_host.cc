@@ -1089,5 +1089,119 @@ void hetrd(int64_t n, R* A, int64_t lda, R* d, R* e, R* tau, int64_t nb) {
 template void hetrd<float>(int64_t, float*, int64_t, float*, float*, float*, int64_t);
 template void hetrd<double>(int64_t, double*, int64_t, double*, double*, double*, int64_t);
 
+//------------------------------------------------------------------------------
+// One-stage bidiagonal reduction (LAPACK gebrd / labrd from the math), the
+// host twin of kernels/gebrd.hip: the same seven steps per column.
+namespace {
+template <typename R>
+void larfg_tail(R alpha, R ss, R& beta, R& tau, R& scale) {
+    beta = alpha; tau = R(0); scale = R(0);
+    if (ss != R(0)) {
+        const R nrm = std::sqrt(alpha * alpha + ss);
+        beta = alpha >= R(0) ? -nrm : nrm;
+        tau = (beta - alpha) / beta;
+        scale = R(1) / (alpha - beta);
+    }
+}
+}  // namespace
+
+template <typename R>
+void gebrd(int64_t m, int64_t n, R* A, int64_t lda, R* d, R* e, R* tauq, R* taup, int64_t nb) {
+    if (n <= 0 || m < n) return;
+    nb = std::max<int64_t>(1, nb);
+    std::vector<R> X(size_t(m) * nb), Y(size_t(n) * nb), t1(nb + 1), t2(nb + 1), y(n), x(m);
+    for (int64_t j0 = 0; j0 < n; j0 += nb) {
+        const int64_t kb = std::min(nb, n - j0);
+        for (int64_t c = 0; c < kb; ++c) {
+            const int64_t i = j0 + c;
+            // 1: A(i:m, i) -= U Y(i,:)^T + X V(:, i)
+            for (int64_t k = 0; k < c; ++k) {
+                const R yi = Y[i + k * n], vi = A[(j0 + k) + i * lda];
+                const R* uk = A + (j0 + k) * lda;
+                const R* xk = X.data() + k * m;
+                for (int64_t r = i; r < m; ++r) A[r + i * lda] -= uk[r] * yi + xk[r] * vi;
+            }
+            // 2: larfg of A(i:m, i); the unit entry is stored
+            R* u = A + i * lda;
+            R ss = 0, scale;
+            for (int64_t r = i + 1; r < m; ++r) ss += u[r] * u[r];
+            larfg_tail<R>(u[i], ss, d[i], tauq[i], scale);
+            for (int64_t r = i + 1; r < m; ++r) u[r] *= scale;
+            u[i] = R(1);
+            if (i == n - 1) break;
+            const int64_t o = i + 1;
+            // 3: y = A(i:m, i+1:n)^T u, and the small dots U^T u, X^T u
+            #pragma omp parallel for schedule(static)
+            for (int64_t j = o; j < n; ++j) {
+                const R* aj = A + j * lda;
+                R s = 0;
+                for (int64_t r = i; r < m; ++r) s += aj[r] * u[r];
+                y[j] = s;
+            }
+            for (int64_t k = 0; k < c; ++k) {
+                const R* uk = A + (j0 + k) * lda;
+                const R* xk = X.data() + k * m;
+                R su = 0, sx = 0;
+                for (int64_t r = i; r < m; ++r) { su += uk[r] * u[r]; sx += xk[r] * u[r]; }
+                t1[k] = su; t2[k] = sx;
+            }
+            // 4: y = tauq (y - Y (U^T u) - V^T (X^T u)); row i: A(i, i+1:n) -= U(i,:) Y^T + X(i,:) V
+            for (int64_t j = o; j < n; ++j) {
+                R s = y[j], rs = 0;
+                for (int64_t k = 0; k < c; ++k) {
+                    const R yk = Y[j + k * n], vk = A[(j0 + k) + j * lda];
+                    s -= yk * t1[k] + vk * t2[k];
+                    rs += yk * A[i + (j0 + k) * lda] + vk * X[i + k * m];
+                }
+                s *= tauq[i];
+                Y[j + c * n] = s;
+                A[i + j * lda] -= rs + s;
+            }
+            // 5: larfg of A(i, i+1:n)
+            ss = 0;
+            for (int64_t j = o + 1; j < n; ++j) ss += A[i + j * lda] * A[i + j * lda];
+            larfg_tail<R>(A[i + o * lda], ss, e[i], taup[i], scale);
+            for (int64_t j = o + 1; j < n; ++j) A[i + j * lda] *= scale;
+            A[i + o * lda] = R(1);
+            // 6: x = A(i+1:m, i+1:n) v, and the small dots Y^T v, V v
+            #pragma omp parallel for schedule(static)
+            for (int64_t rb = o; rb < m; rb += 256) {
+                const int64_t re = std::min(m, rb + 256);
+                for (int64_t r = rb; r < re; ++r) x[r] = 0;
+                for (int64_t j = o; j < n; ++j) {
+                    const R* aj = A + j * lda;
+                    const R vj = A[i + j * lda];
+                    for (int64_t r = rb; r < re; ++r) x[r] += aj[r] * vj;
+                }
+            }
+            for (int64_t k = 0; k <= c; ++k) {
+                R sy = 0, sv = 0;
+                for (int64_t j = o; j < n; ++j) {
+                    sy += Y[j + k * n] * A[i + j * lda];
+                    if (k < c) sv += A[(j0 + k) + j * lda] * A[i + j * lda];
+                }
+                t1[k] = sy; t2[k] = sv;
+            }
+            // 7: x = taup (x - U (Y^T v) - X (V v))
+            for (int64_t k = 0; k <= c; ++k) {
+                const R* uk = A + (j0 + k) * lda;
+                const R* xk = X.data() + k * m;
+                for (int64_t r = o; r < m; ++r) x[r] -= uk[r] * t1[k] + (k < c ? xk[r] * t2[k] : R(0));
+            }
+            for (int64_t r = o; r < m; ++r) X[r + c * m] = taup[i] * x[r];
+        }
+        // trailing update: A22 -= U Y^T + X V
+        const int64_t k1 = j0 + kb;
+        if (k1 < n) {
+            gemm(Op::NoTrans, Op::Trans, m - k1, n - k1, kb, R(-1), A + k1 + j0 * lda, lda, Y.data() + k1, n, R(1),
+                 A + k1 + k1 * lda, lda);
+            gemm(Op::NoTrans, Op::NoTrans, m - k1, n - k1, kb, R(-1), X.data() + k1, m, A + j0 + k1 * lda, lda, R(1),
+                 A + k1 + k1 * lda, lda);
+        }
+    }
+}
+template void gebrd<float>(int64_t, int64_t, float*, int64_t, float*, float*, float*, float*, int64_t);
+template void gebrd<double>(int64_t, int64_t, double*, int64_t, double*, double*, double*, double*, int64_t);
+
 }  // namespace host
 }  // namespace slate

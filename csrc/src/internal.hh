@@ -328,6 +328,26 @@ void unmtr_hetrd_local(lb::Ctx const& c, Side side, Op op, int64_t n, R const* A
 template <typename T>
 void hetrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
 
+/// gebrd's sibling of hetrd_check_operand: the same refusals, worded for the
+/// one-stage bidiagonal reduction
+template <typename T>
+void gebrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
+/// Panel width of the one-stage bidiagonal reduction (gebrd.cc); T factors as hetrd's.
+constexpr int64_t kGebrdPanel = 64;
+/// One-stage bidiagonal reduction of the contiguous local m x n array A (c's
+/// memory), m >= n: A = Q B P^T, B upper bidiagonal (d, e), left reflectors
+/// left in A below the diagonal and right ones right of the superdiagonal,
+/// unit entries stored; tauq, taup (n each) and TQ, TP (kGebrdPanel x n each)
+/// in c's memory, d and e on the host.  One host synchronisation, at the end.
+template <typename R>
+void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std::vector<R>& d, std::vector<R>& e,
+                 R* tauq, R* taup, R* TQ, R* TP);
+/// C (mc x nc) := op(F) C (Left) or C op(F) (Right), F = Q (order m) or P
+/// (order n) of gebrd_local, one lb::larfb per panel; stream-ordered on the device.
+template <typename R>
+void unmbr_gebrd_local(lb::Ctx const& c, Vect vect, Side side, Op op, int64_t m, int64_t n, R const* A, int64_t lda,
+                       R const* Tfac, int64_t mc, int64_t nc, R* C, int64_t ldc);
+
 /// Apply LU pivots to the rows of B (forward: P B; backward: P^T B).
 template <typename T>
 void apply_pivots(Pivots const& pivots, BaseMatrix<T> const& A, Matrix<T>& B, Target target, bool forward);

@@ -64,6 +64,9 @@ struct Params {
     // --method-hetrd two_stage|one_stage: Option::MethodHetrd of heev
     bool has_method_hetrd = false;
     MethodHetrd method_hetrd = MethodHetrd::TwoStage;
+    // --method-gebrd two_stage|one_stage: Option::MethodGebrd of svd / svd_vals
+    bool has_method_gebrd = false;
+    MethodGebrd method_gebrd = MethodGebrd::TwoStage;
     // operand shape flags of the BLAS-3 / triangular routines (reference
     // --uplo --trans --side --diag)
     Uplo uplo = Uplo::Lower;
@@ -1391,6 +1394,52 @@ Result r_hetrd(Case<T>& c, int variant) {   // 0 hetrd (A = Q T Q^T), 1 unmtr_he
 }
 
 template <typename T>
+Result r_gebrd(Case<T>& c, int variant) {   // 0 gebrd (A = Q B P^T), 1 unmbr_gebrd (Q (Q^T C) = C)
+    using R = R_<T>;
+    if (is_complex_v<T>) {
+        Result r; r.skipped = true; r.note = "real types (the one-stage reduction)"; return r;
+    }
+    if (c.m < c.n) {
+        Result r; r.skipped = true; r.note = "m >= n (the one-stage reduction)"; return r;
+    }
+    auto A = c.mat(c.m, c.n);
+    if (A.grid()->size() != 1) {
+        Result r; r.skipped = true; r.note = "a grid of one process (the one-stage reduction)"; return r;
+    }
+    auto A0 = c.copy_of(A);
+    std::vector<R> d, e;
+    TriangularFactors<T> TQ, TP;
+    Result r;
+    const double m = double(c.m), n = double(c.n);
+    if (variant == 0) {
+        r.time = c.timed([&] { gebrd(A, d, e, TQ, TP, c.opts); });
+        r.flops = cfac<T>() * (4.0 * m * n * n - 4.0 / 3 * n * n * n);
+        if (c.P.check) {
+            auto F = c.zeros(c.m, c.n);
+            set<T>(std::function<T(int64_t, int64_t)>([&](int64_t i, int64_t j) {
+                       return i == j ? T(d[i]) : (j == i + 1 ? T(e[i]) : T(0));
+                   }), F, Options{{Option::Target, Target::Host}});
+            unmbr_gebrd(Vect::Q, Side::Left, Op::NoTrans, A, TQ, F, c.opts);
+            unmbr_gebrd(Vect::P, Side::Right, Op::ConjTrans, A, TP, F, c.opts);
+            add(T(-1), A0, T(1), F, c.opts);
+            r.error = c.nrm(F) / (n * c.nrm(A0));
+        }
+        return r;
+    }
+    gebrd(A, d, e, TQ, TP, c.opts);
+    auto C = c.mat(c.m, c.P.nrhs);
+    auto C0 = c.copy_of(C);
+    r.time = c.timed([&] { unmbr_gebrd(Vect::Q, Side::Left, Op::ConjTrans, A, TQ, C, c.opts); });
+    r.flops = cfac<T>() * 2.0 * m * n * c.P.nrhs;
+    if (c.P.check) {
+        unmbr_gebrd(Vect::Q, Side::Left, Op::NoTrans, A, TQ, C, c.opts);
+        add(T(-1), C0, T(1), C, c.opts);
+        r.error = c.nrm(C) / (m * c.nrm(C0));
+    }
+    return r;
+}
+
+template <typename T>
 Result r_hb2st(Case<T>& c, int variant) {   // 0 hb2st (Frobenius norm preserved), 1 unmtr_hb2st
     using R = R_<T>;
     auto A = herm_of(c, c.n);
@@ -1961,6 +2010,8 @@ std::map<std::string, Fn<T>> routines() {
         {"unmtr_he2hb", [](Case<T>& c) { return r_he2hb<T>(c, 1); }},
         {"hetrd", [](Case<T>& c) { return r_hetrd<T>(c, 0); }},
         {"unmtr_hetrd", [](Case<T>& c) { return r_hetrd<T>(c, 1); }},
+        {"gebrd", [](Case<T>& c) { return r_gebrd<T>(c, 0); }},
+        {"unmbr_gebrd", [](Case<T>& c) { return r_gebrd<T>(c, 1); }},
         {"hb2st", [](Case<T>& c) { return r_hb2st<T>(c, 0); }},
         {"unmtr_hb2st", [](Case<T>& c) { return r_hb2st<T>(c, 1); }},
         {"ge2tb", r_ge2tb<T>},
@@ -2033,6 +2084,8 @@ int run_type(Params const& P, char tc, std::string const& name) {
                 if (with_method_svd) c.opts[Option::MethodSVD] = P.method_svd;
                 const bool with_method_hetrd = P.has_method_hetrd && name == "heev";
                 if (with_method_hetrd) c.opts[Option::MethodHetrd] = P.method_hetrd;
+                const bool with_method_gebrd = P.has_method_gebrd && (name == "svd" || name == "svd_vals");
+                if (with_method_gebrd) c.opts[Option::MethodGebrd] = P.method_gebrd;
                 Result r;
                 std::string status;
                 try {
@@ -2058,6 +2111,9 @@ int run_type(Params const& P, char tc, std::string const& name) {
                                          : "") +
                         (with_method_hetrd ? std::string("  method_hetrd=") +
                                                  (P.method_hetrd == MethodHetrd::OneStage ? "one_stage" : "two_stage")
+                                           : "") +
+                        (with_method_gebrd ? std::string("  method_gebrd=") +
+                                                 (P.method_gebrd == MethodGebrd::OneStage ? "one_stage" : "two_stage")
                                            : "");
                     std::printf("%-16s %-4c %7lld %7lld %7lld %5lld %2d %2d %s %10.4f %11.2f  %s%s%s%s\n", name.c_str(),
                                 tc, (long long)c.m, (long long)c.n, (long long)c.k, (long long)nb, g->p(), g->q(), es,
@@ -2090,7 +2146,7 @@ void usage() {
         "       [--uplo l|u] [--trans n|t|c] [--side l|r] [--diag n|u] [--cond C] [--ib IB]\n"
         "       [--nonuniform-nb y|n] [--go c|r] [--do r|c]\n"
         "       [--gemm-precision native|bf16|bf16x3|bf16x6] [--method-svd qr|dc]\n"
-        "       [--method-hetrd two_stage|one_stage]\n"
+        "       [--method-hetrd two_stage|one_stage] [--method-gebrd two_stage|one_stage]\n"
         "routines:");
     for (auto const& kv : routines<double>()) std::printf(" %s", kv.first.c_str());
     std::printf("\n");
@@ -2166,6 +2222,15 @@ int main(int argc, char** argv) {
             }
             P.method_hetrd = v == "one_stage" ? MethodHetrd::OneStage : MethodHetrd::TwoStage;
             P.has_method_hetrd = true;
+        }
+        else if (a == "--method-gebrd") {
+            std::string v = val();
+            for (auto& ch : v) ch = char(std::tolower((unsigned char)ch));
+            if (v != "two_stage" && v != "one_stage") {
+                std::fprintf(stderr, "--method-gebrd: two_stage or one_stage\n"); usage(); return 2;
+            }
+            P.method_gebrd = v == "one_stage" ? MethodGebrd::OneStage : MethodGebrd::TwoStage;
+            P.has_method_gebrd = true;
         }
         else if (!a.empty() && a[0] != '-') rlist = rlist.empty() ? a : rlist + "," + a;
         else { usage(); return 2; }

@@ -16,6 +16,8 @@ Uplo = _slate.Uplo
 Job = _slate.Job
 MethodSVD = _slate.MethodSVD
 MethodHetrd = _slate.MethodHetrd
+MethodGebrd = _slate.MethodGebrd
+Vect = _slate.Vect
 Diag = _slate.Diag
 Side = _slate.Side
 Norm = _slate.Norm

@@ -6,7 +6,7 @@ from ._wrap import call
 __all__ = ["heev", "hegv", "hegst", "svd", "svd_vals", "gesvd", "eig", "eig_vals", "he2hb", "hb2st", "sterf",
            "steqr", "stedc", "ge2tb", "tb2bd", "bdsqr", "syev", "sygv", "hb2st_band", "unmtr_hb2st",
            "unmtr_he2hb", "tb2bd_band", "unmbr_tb2bd", "unmbr_ge2tb", "steqr2", "stedc_matrix", "bdsqr_matrix",
-           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd"]
+           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd", "gebrd", "unmbr_gebrd"]
 
 
 def heev(A, Z=None, target=None, **kw):
@@ -30,7 +30,9 @@ def hegst(itype, A, B, target=None, **kw):
 def svd(A, U=None, VT=None, target=None, **kw):
     """Singular values (descending numpy array); thin U (m x k) and VT
     (k x n), k = min(m, n), filled when given.  method_svd="qr" (bidiagonal
-    QR iteration, default) or "dc" (divide and conquer, bdsdc)."""
+    QR iteration, default) or "dc" (divide and conquer, bdsdc).
+    method_gebrd="two_stage" (ge2tb + tb2bd, default) or "one_stage" (gebrd:
+    real types, one process), also for svd_vals and gesvd."""
     import numpy as np
     return np.asarray(call("svd", A, A, U, VT, target=target, **kw))
 
@@ -178,3 +180,22 @@ def hetrd(A, target=None, **kw):
 def unmtr_hetrd(side, op, A, T, C, target=None, **kw):
     """C := op(Q) C (Side.Left) or C op(Q) (Side.Right) with Q from hetrd(A)."""
     return call("unmtr_hetrd", C, side, op, A, T, C, target=target, **kw)
+
+
+def gebrd(A, target=None, **kw):
+    """One-stage bidiagonal reduction of a real m x n matrix of one process,
+    m >= n: returns (d, e, TQ, TP) with A = Q B P^T, B upper bidiagonal with
+    diagonal d and superdiagonal e; the reflectors stay in A, TQ and TP hold
+    the block-reflector factors for unmbr_gebrd."""
+    import numpy as np
+    d, e, TQ, TP = call("gebrd", A, A, target=target, **kw)
+    return np.asarray(d), np.asarray(e), TQ, TP
+
+
+def unmbr_gebrd(vect, side, op, A, T, C, target=None, **kw):
+    """C := op(F) C (Side.Left) or C op(F) (Side.Right) with F = Q ("q", T =
+    TQ) or F = P ("p", T = TP) from gebrd(A)."""
+    from .._core import Vect
+    if isinstance(vect, str):
+        vect = {"q": Vect.Q, "p": Vect.P}[vect.lower()]
+    return call("unmbr_gebrd", C, vect, side, op, A, T, C, target=target, **kw)

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "symv_lower", "hetrd_stats", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "gemv_t_block", "gemv_n_block", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -114,6 +114,52 @@ def symv_lower(A, x, offset: int = 0, repeat: int = 1):
         _slate.lb_symv_lower(_suffix(A), m, pa + (offset + offset * lda) * A.element_size(), lda, x.data_ptr(),
                              y.data_ptr(), repeat)
     return y
+
+
+def gebrd_stats() -> dict:
+    """Counters of the last one-stage bidiagonal reduction of this process
+    (gebrd, or svd with method_gebrd="one_stage"): `columns`, `panels`,
+    `host_syncs` inside the reduction and the launches of its seven column
+    kernels, launches_column / _larfg_u / _pass1 / _finish_y / _larfg_v /
+    _pass2 / _finish_x (zero on the host target).  ms_pass1 / ms_pass2 /
+    ms_panel / ms_gemm / ms_larft are device milliseconds from events between
+    the kernels, recorded only when SLATE_GEBRD_PROFILE=1 is in the environment
+    (zero otherwise)."""
+    return _slate.gebrd_stats()
+
+
+def _gemv_block(trans, A, x, row_offset, col_offset, repeat, use_lb):
+    import torch
+    pa, rows, cols, lda = _cm(A)
+    mr, nc = rows - row_offset, cols - col_offset
+    assert 0 <= row_offset and 0 <= col_offset and mr >= 0 and nc >= 0
+    assert x.numel() == (mr if trans else nc) and x.dtype == A.dtype and x.is_contiguous()
+    if x.is_cuda:
+        torch.cuda.current_stream(x.device).synchronize()
+    y = torch.empty(nc if trans else mr, dtype=A.dtype, device=A.device)
+    torch.cuda.current_stream(A.device).synchronize()
+    if mr > 0 and nc > 0:
+        _slate.lb_gemv_block(_suffix(A), trans, mr, nc, pa + (row_offset + col_offset * lda) * A.element_size(), lda,
+                             x.data_ptr(), y.data_ptr(), repeat, use_lb)
+    else:
+        y.zero_()
+    return y
+
+
+def gemv_t_block(A, x, row_offset: int = 0, col_offset: int = 0, repeat: int = 1, use_lb: bool = False):
+    """y = B^T x on the device, B the block of the column-major matrix A that
+    starts at (row_offset, col_offset) and runs to its last row and column:
+    pass 1 of the one-stage bidiagonal reduction.  Nothing outside the block
+    is loaded.  float32 or float64; two calls give the same bits.  repeat > 1
+    enqueues the same product that many times before the one synchronisation
+    (timing); use_lb=True runs lb::gemv instead (the yardstick)."""
+    return _gemv_block(True, A, x, row_offset, col_offset, repeat, use_lb)
+
+
+def gemv_n_block(A, x, row_offset: int = 0, col_offset: int = 0, repeat: int = 1, use_lb: bool = False):
+    """y = B x on the device, B as in gemv_t_block: pass 2 of the one-stage
+    bidiagonal reduction."""
+    return _gemv_block(False, A, x, row_offset, col_offset, repeat, use_lb)
 
 
 def gemm_async(queue: int, opA: str, opB: str, alpha, A, B, beta, C):

@@ -85,8 +85,14 @@ class Ctx:
         mh = getattr(self.a, "method_hetrd", None)
         return mh if mh and self.name == "heev" else None
 
+    def method_gebrd(self):
+        mg = getattr(self.a, "method_gebrd", None)
+        return mg if mg and self.name in ("svd", "svd_vals") else None
+
     def opts(self):
         o = dict(target=self.target, lookahead=self.a.lookahead)
+        if self.method_gebrd():
+            o["method_gebrd"] = self.method_gebrd()
         if self.method_hetrd():
             o["method_hetrd"] = self.method_hetrd()
         if self.gemm_precision():
@@ -317,6 +323,42 @@ def r_unmtr_hetrd(c):
     return t, err
 
 
+def _bidiag(d, e, m):
+    b = np.zeros((m, len(d)), dtype=np.asarray(d).dtype)
+    b[:len(d), :] = np.diag(d) + np.diag(e, 1)
+    return b
+
+
+def r_gebrd(c):
+    _real_only(c)
+    if c.m < c.n:
+        raise NotImplementedError("m >= n (the one-stage reduction)")
+    a, A = c.mat(c.m, c.n)
+    t, (d, e, TQ, TP) = _timed(lambda: M.gebrd(A, target=c.target))
+    err = None
+    if c.a.check:
+        F = core.from_numpy(_bidiag(d, e, c.m).astype(c.dt), nb=c.nb, target=c.target)
+        M.unmbr_gebrd("q", core.Side.Left, core.Op.NoTrans, A, TQ, F, target=c.target)
+        M.unmbr_gebrd("p", core.Side.Right, core.Op.Trans, A, TP, F, target=c.target)
+        err = np.linalg.norm(core.to_numpy(F) - a) / (np.linalg.norm(a) * c.n)
+    return t, err
+
+
+def r_unmbr_gebrd(c):
+    _real_only(c)
+    if c.m < c.n:
+        raise NotImplementedError("m >= n (the one-stage reduction)")
+    a, A = c.mat(c.m, c.n)
+    d, e, TQ, TP = M.gebrd(A, target=c.target)
+    b, C = c.mat(c.m, c.a.nrhs)
+    t, _ = _timed(lambda: M.unmbr_gebrd("q", core.Side.Left, core.Op.Trans, A, TQ, C, target=c.target))
+    err = None
+    if c.a.check:
+        M.unmbr_gebrd("q", core.Side.Left, core.Op.NoTrans, A, TQ, C, target=c.target)
+        err = resid(core.to_numpy(C), b)
+    return t, err
+
+
 def r_svd(c):
     a, A = c.mat(c.m, c.n)
     k = min(c.m, c.n)
@@ -393,6 +435,8 @@ ROUTINES = {
     "heev": (r_heev, lambda m, n, k: 4.0 / 3.0 * n ** 3),
     "hetrd": (r_hetrd, lambda m, n, k: 4.0 / 3.0 * n ** 3),
     "unmtr_hetrd": (r_unmtr_hetrd, lambda m, n, k: 0.0),
+    "gebrd": (r_gebrd, lambda m, n, k: 4.0 * m * n * n - 4.0 / 3.0 * n ** 3),
+    "unmbr_gebrd": (r_unmbr_gebrd, lambda m, n, k: 0.0),
     "svd": (r_svd, lambda m, n, k: 8.0 / 3.0 * n ** 3),
     "hesv": (r_hesv, lambda m, n, k: n ** 3 / 3.0),
     "gbsv": (r_gbsv, lambda m, n, k: 0.0),
@@ -421,6 +465,8 @@ def main(argv=None):
                     help="bidiagonal stage of svd: QR iteration (default) or divide and conquer")
     ap.add_argument("--method-hetrd", default=None, choices=["two_stage", "one_stage"],
                     help="tridiagonal reduction of heev: two stages (default) or the one-stage hetrd")
+    ap.add_argument("--method-gebrd", default=None, choices=["two_stage", "one_stage"],
+                    help="bidiagonal reduction of svd: two stages (default) or the one-stage gebrd")
     a = ap.parse_args(argv)
     a.check = a.check.lower().startswith("y")
     world = parallel.world_size()
@@ -461,7 +507,8 @@ def main(argv=None):
                                   f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}"
                                   + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else "")
                                   + (f"  method_svd={c.method_svd()}" if c.method_svd() else "")
-                                  + (f"  method_hetrd={c.method_hetrd()}" if c.method_hetrd() else ""),
+                                  + (f"  method_hetrd={c.method_hetrd()}" if c.method_hetrd() else "")
+                                  + (f"  method_gebrd={c.method_gebrd()}" if c.method_gebrd() else ""),
                                   flush=True)
     if rank == 0:
         print(f"# {nfail} failed" if nfail else "# all tests passed")

@@ -1,0 +1,51 @@
+"""Multi-process check of the one-stage bidiagonal reduction's scope, run
+under torch.distributed.run by test_gebrd.py (as hetrd_worker.py is by
+test_hetrd.py).
+
+usage: gebrd_worker.py P Q TARGET
+On a grid of more than one process svd(method_gebrd="one_stage") and gebrd
+raise NotImplemented with a message that names the grid; the two-stage
+default still solves the same matrix.
+"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+sys.path.insert(0, HERE)
+
+import torch  # noqa: F401,E402  (HIP runtime first)
+import slate_d35_amd as s  # noqa: E402
+from slate_d35_amd import parallel  # noqa: E402
+from helpers import rnd  # noqa: E402
+
+
+def refused(fn):
+    try:
+        fn()
+    except Exception as ex:  # slate::NotImplemented
+        msg = str(ex)
+        assert "grid of one process" in msg and "not implemented" in msg.lower(), msg
+        return True
+    return False
+
+
+def main():
+    p, q, tg = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
+    parallel.init_grid(p, q, transport=os.environ.get("SLATE_TRANSPORT", "auto"))
+    n, nb = 96, 32
+    a = rnd(n, n, np.float64, 4)
+    assert refused(lambda: s.svd_vals(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg, method_gebrd="one_stage"))
+    assert refused(lambda: s.gebrd(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg))
+    w = s.svd_vals(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg)
+    ref = np.linalg.svd(a, compute_uv=False)
+    assert np.abs(w - ref).max() <= 1e-10 * np.abs(ref).max()
+    parallel.finalize()
+    if parallel.world_rank() == 0:
+        print("GEBRD_REFUSED_OK", p, q, tg, flush=True)
+
+
+if __name__ == "__main__":
+    main()
