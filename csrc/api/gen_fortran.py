@@ -11,7 +11,8 @@ prototype, and maps C types onto iso_c_binding kinds:
   scalar_t                                    -> real or complex kind, value
   slate_Side / Op / Uplo / Diag / Norm / Target -> character(kind=c_char), value
   T* (data arrays, Lambda, Sigma)             -> assumed-size array T(*)
-  int* (iteration count)                      -> integer(c_int) by reference
+  int* / int64_t* (iteration count, nfound)   -> integer kinds by reference
+  float* / double* (d, e, w of stebz / bdsbz) -> assumed-size array
   const char* (matgen kind)                   -> character(kind=c_char) s(*)
   slate_Options const*                        -> type(slate_Options) opts(*)
 
@@ -30,7 +31,7 @@ PREC = {  # suffix: (scalar kind decl, real kind decl, kind names to import)
     "c32": ("complex(c_float_complex)", "real(c_float)", {"c_float_complex", "c_float"}),
     "c64": ("complex(c_double_complex)", "real(c_double)", {"c_double_complex", "c_double"}),
 }
-CHAR_TYPES = {"slate_Target", "slate_Op", "slate_Uplo", "slate_Diag", "slate_Side", "slate_Norm"}
+CHAR_TYPES = {"slate_Target", "slate_Op", "slate_Uplo", "slate_Diag", "slate_Side", "slate_Norm", "slate_Range"}
 
 
 def strip_comments(s):
@@ -87,6 +88,8 @@ def ftype(ctype, name, kinds):
             "uint64_t": ("integer(c_int64_t)", "c_int64_t"), "double": ("real(c_double)", "c_double"),
             "float": ("real(c_float)", "c_float")}[t]
     kinds.add(base[1])
+    if ptr and t in ("float", "double"):
+        return f"{base[0]} :: {name}(*)"
     return f"{base[0]} :: {name}" if ptr else f"{base[0]}, value :: {name}"
 
 
@@ -118,7 +121,7 @@ def interface(ret, name, args):
 
 
 def options(text):
-    return re.findall(r"(slate_(?:Option|GemmPrecision|MethodSVD|MethodHetrd|MethodGebrd)_\w+)\s*=\s*(\d+)", text)
+    return re.findall(r"(slate_(?:Option|GemmPrecision|MethodSVD|MethodEig|MethodHetrd|MethodGebrd)_\w+)\s*=\s*(\d+)", text)
 
 
 def main():

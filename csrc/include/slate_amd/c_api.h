@@ -45,8 +45,17 @@ enum { slate_MethodGebrd_TwoStage = 50, slate_MethodGebrd_OneStage = 49 };
 enum { slate_MethodHetrd_TwoStage = 50, slate_MethodHetrd_OneStage = 49 };
 
 /* ivalue of slate_Option_MethodSVD (slate::MethodSVD): bidiagonal stage of
- * slate_svd* with vectors, QR iteration (default) or divide and conquer */
-enum { slate_MethodSVD_QR = 81, slate_MethodSVD_DC = 68 };
+ * slate_svd* with vectors, QR iteration (default) or divide and conquer;
+ * Bisection: values only (U and VT NULL), Sturm-count bisection */
+enum { slate_MethodSVD_QR = 81, slate_MethodSVD_DC = 68, slate_MethodSVD_Bisection = 66 };
+
+/* ivalue of slate_Option_MethodEig (slate::MethodEig): tridiagonal stage of
+ * slate_hermitian_eig*, divide and conquer (default) or QR iteration with
+ * vectors; Bisection: values only (Z NULL), Sturm-count bisection */
+enum { slate_MethodEig_QR = 81, slate_MethodEig_DC = 68, slate_MethodEig_Bisection = 66 };
+
+/* range of slate_stebz_* / slate_bdsbz_* (slate::Range) */
+typedef char slate_Range;    /* 'A' all, 'V' values in [vl, vu), 'I' indices il .. iu (1-based) */
 
 /* ivalue of slate_Option_GemmPrecision (slate::GemmPrecision): arithmetic of
  * the fp32 trailing updates of gemm, the LU family and Cholesky; the mixed
@@ -198,6 +207,20 @@ int64_t slate_lu_solve_mixed_r64(slate_Matrix_r64 A, slate_Matrix_r64 B, slate_M
                                  int nopts, slate_Options const* opts);
 int64_t slate_chol_solve_mixed_r64(slate_Uplo uplo, slate_Matrix_r64 A, slate_Matrix_r64 B, slate_Matrix_r64 X,
                                    int* iter, int nopts, slate_Options const* opts);
+
+/* Sturm-count bisection on plain arrays (slate::stebz / slate::bdsbz): d of n,
+ * e of n - 1.  stebz: eigenvalues of the symmetric tridiagonal, ascending;
+ * bdsbz: singular values of the upper bidiagonal, descending, indices counted
+ * from the largest.  w has room for n values (il .. iu: iu - il + 1 suffice);
+ * *nfound receives the number written.  Returns 0, or -1 (slate_last_error). */
+int slate_stebz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t iu, int64_t n, float const* d,
+                    float const* e, int64_t* nfound, float* w, int nopts, slate_Options const* opts);
+int slate_stebz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
+                    double const* e, int64_t* nfound, double* w, int nopts, slate_Options const* opts);
+int slate_bdsbz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t iu, int64_t n, float const* d,
+                    float const* e, int64_t* nfound, float* s, int nopts, slate_Options const* opts);
+int slate_bdsbz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
+                    double const* e, int64_t* nfound, double* s, int nopts, slate_Options const* opts);
 
 #ifdef __cplusplus
 }

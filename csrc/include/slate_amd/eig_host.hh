@@ -68,6 +68,18 @@ int64_t steqr(int64_t n, R* d, R* e, T* Z, int64_t ldz, int64_t zrows);
 template <typename R>
 int64_t sterf(int64_t n, R* d, R* e);
 
+/// Host twins of kernels/stebz.hip over slate_amd/sturm.hh, on a tridiagonal
+/// (d of n, e2 = e^2 of n - 1) already scaled to unit max-norm.
+/// cnt[j] = N(x[j]), OpenMP across shifts.
+template <typename R>
+void sturm_counts(int64_t n, const R* d, const R* e2, R pivmin, int64_t nx, const R* x, int64_t* cnt);
+/// Eigenvalues [k0, k1) (0-based, ascending) by plain bisection from the
+/// start interval [lo, hi], OpenMP across eigenvalues: w[k - k0].  Stops as
+/// sturm::converged(abstol, floor) says.  Returns the most steps a value took.
+template <typename R>
+int64_t stebz_range(int64_t n, const R* d, const R* e2, R pivmin, R lo, R hi, R abstol, R floor, int64_t k0,
+                    int64_t k1, R* w);
+
 /// Divide and conquer: eigenvalues ascending in d, eigenvectors in Q (n x n).
 template <typename R>
 int64_t stedc(int64_t n, R* d, R* e, R* Q, int64_t ldq);

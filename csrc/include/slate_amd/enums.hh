@@ -40,12 +40,19 @@ enum class GridOrder : char { Col = 'C', Row = 'R', Unknown = 'U' };
 /// Layout conversion request (enums.hh:105).
 enum class LayoutConvert : char { ColMajor = 'C', RowMajor = 'R', None = 'N' };
 
-/// Eigenvalue method (enums.hh MethodEig).
-enum class MethodEig : char { QR = 'Q', DC = 'D' };
+/// Eigenvalue method (enums.hh MethodEig).  Bisection (not in the reference):
+/// values only, Sturm-count bisection (stebz) in place of sterf.
+enum class MethodEig : char { QR = 'Q', DC = 'D', Bisection = 'B' };
 
 /// Bidiagonal SVD method of svd with vectors: implicit-shift QR iteration
-/// (bdsqr, default) or divide and conquer (bdsdc).  Not in the reference.
-enum class MethodSVD : char { QR = 'Q', DC = 'D' };
+/// (bdsqr, default) or divide and conquer (bdsdc); Bisection: values only,
+/// Sturm-count bisection on the Golub-Kahan form (bdsbz) in place of the
+/// values-only QR iteration.  Not in the reference.
+enum class MethodSVD : char { QR = 'Q', DC = 'D', Bisection = 'B' };
+
+/// Which eigenvalues / singular values stebz and bdsbz compute (LAPACK's
+/// range): all, those in [vl, vu), or those with index il .. iu.
+enum class Range : char { All = 'A', Value = 'V', Index = 'I' };
 
 /// Tridiagonal reduction of heev / syev / hegv / sygv: two stages (he2hb on
 /// the device, the bulge chase hb2st on the host; default) or the one-stage

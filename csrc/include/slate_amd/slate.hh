@@ -323,6 +323,48 @@ void unmbr_ge2tb(Side side, Op op, Matrix<T>& A, std::vector<TriangularFactors<T
 /// Tridiagonal eigenvalues only (root-free QL).
 template <typename R>
 void sterf(std::vector<R>& D, std::vector<R>& E, Options const& opts = {});
+/// Eigenvalues of the symmetric tridiagonal (D of n, E of n - 1) by Sturm-count
+/// bisection (src/stebz.cc, slate_amd/sturm.hh), ascending in W, which is
+/// sized to the number found.  Range::All: all n; Range::Index: the 1-based
+/// il <= k <= iu of the ascending order; Range::Value: those with
+/// N(vl) < k <= N(vu), N(x) the number of eigenvalues below x, i.e. [vl, vu)
+/// up to rounding at the end points.  A subset has the bits of the same
+/// entries of the full set.  Accuracy is absolute, a few eps max|T_ij|.
+/// Target::Devices: one kernel launch on the calling context's device (two
+/// for Range::Value) and one host synchronisation, the fetch of the result;
+/// host targets: the same arithmetic with OpenMP across eigenvalues.  D and E
+/// are replicated host vectors: on a grid every process computes all values
+/// itself.  n = 0 and n = 1 are accepted; an all-zero matrix returns zeros
+/// without a launch.  Throws Exception, before any launch, on a non-finite
+/// entry, on vl >= vu (Value) or on il / iu outside 1 <= il <= iu <= n (Index).
+template <typename R>
+void stebz(Range range, R vl, R vu, int64_t il, int64_t iu, std::vector<R> const& D, std::vector<R> const& E,
+           std::vector<R>& W, Options const& opts = {});
+/// Singular values of the upper bidiagonal (D of n, E of n - 1) by the same
+/// bisection on its Golub-Kahan tridiagonal of order 2n, DESCENDING in S as
+/// svd returns them; Range::Index counts in that order (il = 1 is the
+/// largest), Range::Value keeps the values in [vl, vu).  The signs of D and E
+/// do not matter.  Accuracy is relative, about (2n - 1) eps, for values above
+/// sqrt(safe_min) max|B_ij|; below that floor a value is the midpoint of its
+/// last interval (absolute accuracy), which is what an exact zero singular
+/// value returns.  Targets, limits and refusals as for stebz.
+template <typename R>
+void bdsbz(Range range, R vl, R vu, int64_t il, int64_t iu, std::vector<R> const& D, std::vector<R> const& E,
+           std::vector<R>& S, Options const& opts = {});
+/// N(x_j), the number of eigenvalues of tridiag(D, E) below x_j, per shift.
+template <typename R>
+std::vector<int64_t> sturm_count(std::vector<R> const& D, std::vector<R> const& E, std::vector<R> const& x,
+                                 Options const& opts = {});
+/// Counters of the last stebz / bdsbz of this process (also through heev /
+/// svd with the Bisection methods): order of the tridiagonal counted (2n for
+/// bdsbz), values returned, trial points per step P (1 on the host), the most
+/// steps any value took, kernel launches and host synchronisations (both
+/// zero on the host target).  P comes from n and the device's CU count;
+/// SLATE_STEBZ_POINTS in the environment (1, 2, 4 .. 64) overrides it.
+struct StebzStats {
+    int64_t n = 0, values = 0, points = 0, steps = 0, launches = 0, host_syncs = 0;
+};
+StebzStats stebz_stats();
 /// Tridiagonal QL/QR; with jobz = Vec, Z := Z * (eigenvectors).
 template <typename T>
 void steqr2(Job jobz, std::vector<real_type<T>>& D, std::vector<real_type<T>>& E, Matrix<T>& Z,

@@ -13,6 +13,7 @@
 #include "dev_types.hh"
 #include "matgen_entry.hh"
 #include "slate_amd/secular.hh"
+#include "slate_amd/sturm.hh"
 
 namespace slate_amd {
 namespace dev {
@@ -186,6 +187,29 @@ struct BdsdcPlace {
 template <typename T>
 void bdsdc_place(BdsdcPlace const& p, const rt<T>* src, int64_t lds, const T* phase, T* dst, int64_t ldd,
                  hipStream_t s);
+
+// ---- Sturm-count bisection (stebz.hip), float and double; arithmetic of slate_amd/sturm.hh
+/// cnt[j] = N(x[j]), j < nx, for the tridiagonal (d of n, e2 = e^2 of n - 1) already scaled to unit max-norm
+template <typename R>
+void sturm_count(int64_t n, const R* d, const R* e2, R pivmin, int64_t nx, const R* x, int64_t* cnt, hipStream_t s);
+/// the refinement of the eigenvalues [k0, k1) (0-based, ascending) in one launch: w[k - k0] and steps[k - k0].
+/// cnt != nullptr: [k0, k1) = wanted_of_counts(cnt[0], cnt[1], kmin), read on the device.
+template <typename R>
+struct StebzRefine {
+    int64_t n = 0;
+    const R *d = nullptr, *e2 = nullptr;
+    R lo = 0, hi = 0;                  // start interval of every eigenvalue
+    R pivmin = 0, abstol = 0, floor = 0;
+    int64_t k0 = 0, k1 = 0, kmin = 0;
+    const int64_t* cnt = nullptr;
+    int points = 1;                    // P: 1, 2, 4, .. 64
+    int max_steps = 0;
+    R* w = nullptr;
+    int32_t* steps = nullptr;
+};
+/// max_values: k1 - k0, or with cnt the most it can be (n - kmin)
+template <typename R>
+void stebz_refine(StebzRefine<R> const& a, int64_t max_values, hipStream_t s);
 
 // ---- one-stage tridiagonal reduction (hetrd.hip), float and double
 /// y = A x for the order-m symmetric block of which only the lower triangle is

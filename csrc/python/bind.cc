@@ -170,13 +170,19 @@ Options to_options(py::dict d) {
         else if (k == "method_gels") o[Option::MethodGels] = meth(v, MethodGels::str2method);
         else if (k == "method_cholqr") o[Option::MethodCholQR] = meth(v, MethodCholQR::str2method);
         else if (k == "method_hemm") o[Option::MethodHemm] = meth(v, MethodHemm::str2method);
-        else if (k == "method_eig") o[Option::MethodEig] = OptionValue(int64_t(v.cast<std::string>()[0]));
+        else if (k == "method_eig") {
+            std::string mname = v.cast<std::string>();
+            for (auto& ch : mname) ch = char(std::tolower((unsigned char)ch));
+            if (mname == "bisection") o[Option::MethodEig] = MethodEig::Bisection;
+            else o[Option::MethodEig] = OptionValue(int64_t(v.cast<std::string>()[0]));
+        }
         else if (k == "method_svd") {
             std::string mname = v.cast<std::string>();
             for (auto& ch : mname) ch = char(std::tolower((unsigned char)ch));
             if (mname == "qr") o[Option::MethodSVD] = MethodSVD::QR;
             else if (mname == "dc") o[Option::MethodSVD] = MethodSVD::DC;
-            else throw Exception("method_svd: \"qr\" or \"dc\", not " + mname);
+            else if (mname == "bisection") o[Option::MethodSVD] = MethodSVD::Bisection;
+            else throw Exception("method_svd: \"qr\", \"dc\" or \"bisection\", not " + mname);
         }
         else if (k == "method_hetrd") {
             std::string mname = v.cast<std::string>();
@@ -438,7 +444,11 @@ PYBIND11_MODULE(_slate, m) {
     py::enum_<GridOrder>(m, "GridOrder").value("Col", GridOrder::Col).value("Row", GridOrder::Row);
     py::enum_<Equed>(m, "Equed").value("None_", Equed::None).value("Row", Equed::Row).value("Col", Equed::Col)
         .value("Both", Equed::Both);
-    py::enum_<MethodSVD>(m, "MethodSVD").value("QR", MethodSVD::QR).value("DC", MethodSVD::DC);
+    py::enum_<MethodSVD>(m, "MethodSVD").value("QR", MethodSVD::QR).value("DC", MethodSVD::DC)
+        .value("Bisection", MethodSVD::Bisection);
+    py::enum_<MethodEig>(m, "MethodEig").value("QR", MethodEig::QR).value("DC", MethodEig::DC)
+        .value("Bisection", MethodEig::Bisection);
+    py::enum_<Range>(m, "Range").value("All", Range::All).value("Value", Range::Value).value("Index", Range::Index);
     py::enum_<MethodHetrd>(m, "MethodHetrd").value("TwoStage", MethodHetrd::TwoStage)
         .value("OneStage", MethodHetrd::OneStage);
     py::enum_<MethodGebrd>(m, "MethodGebrd").value("TwoStage", MethodGebrd::TwoStage)
@@ -657,6 +667,54 @@ PYBIND11_MODULE(_slate, m) {
         r["level_columns"] = st.level_columns;
         r["level_deflated"] = st.level_deflated;
         return r;
+    });
+    m.def("stebz_stats", []() {
+        const StebzStats st = stebz_stats();
+        py::dict r;
+        r["n"] = st.n;
+        r["values"] = st.values;
+        r["points"] = st.points;
+        r["steps"] = st.steps;
+        r["launches"] = st.launches;
+        r["host_syncs"] = st.host_syncs;
+        return r;
+    });
+    // Sturm-count bisection on plain vectors: type "s" or "d", bidiagonal: bdsbz instead of stebz
+    m.def("stebz", [](std::string type, bool bidiagonal, Range range, double vl, double vu, int64_t il, int64_t iu,
+                      std::vector<double> d, std::vector<double> e, py::dict opts) -> py::object {
+        if (type != "d" && type != "s") throw Exception("stebz / bdsbz: float32 or float64");
+        const Options o = to_options(opts);
+        if (type == "d") {
+            std::vector<double> w;
+            {
+                py::gil_scoped_release r;
+                if (bidiagonal) bdsbz<double>(range, vl, vu, il, iu, d, e, w, o);
+                else stebz<double>(range, vl, vu, il, iu, d, e, w, o);
+            }
+            return py::array_t<double>(py::ssize_t(w.size()), w.data());
+        }
+        std::vector<float> df(d.begin(), d.end()), ef(e.begin(), e.end()), w;
+        {
+            py::gil_scoped_release r;
+            if (bidiagonal) bdsbz<float>(range, float(vl), float(vu), il, iu, df, ef, w, o);
+            else stebz<float>(range, float(vl), float(vu), il, iu, df, ef, w, o);
+        }
+        return py::array_t<float>(py::ssize_t(w.size()), w.data());
+    });
+    m.def("sturm_count", [](std::string type, std::vector<double> d, std::vector<double> e, std::vector<double> x,
+                            py::dict opts) {
+        if (type != "d" && type != "s") throw Exception("sturm_count: float32 or float64");
+        const Options o = to_options(opts);
+        std::vector<int64_t> c;
+        {
+            py::gil_scoped_release r;
+            if (type == "d") c = sturm_count<double>(d, e, x, o);
+            else {
+                std::vector<float> df(d.begin(), d.end()), ef(e.begin(), e.end()), xf(x.begin(), x.end());
+                c = sturm_count<float>(df, ef, xf, o);
+            }
+        }
+        return py::array_t<int64_t>(py::ssize_t(c.size()), c.data());
     });
     m.def("queue_sync", [](int q) { slate_hip_call(hipStreamSynchronize(device::queue(q))); },
           py::call_guard<py::gil_scoped_release>());

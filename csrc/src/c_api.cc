@@ -249,3 +249,40 @@ int64_t slate_chol_solve_mixed_r64(slate_Uplo uplo, slate_Matrix_r64 A, slate_Ma
         return info; }, int64_t(-1));
 }
 }  // extern "C"
+
+namespace {
+template <typename R>
+int bisect_c(bool bidiagonal, slate_Range range, R vl, R vu, int64_t il, int64_t iu, int64_t n, R const* d, R const* e,
+             int64_t* nfound, R* w, int no, slate_Options const* o) {
+    return guarded([&]() {
+        slate_error_if_msg(n < 0 || (n > 0 && !d) || (n > 1 && !e), "stebz / bdsbz: n < 0 or a null array");
+        std::vector<R> D(d, d + n), E(e, e + std::max<int64_t>(n - 1, 0)), W;
+        if (bidiagonal) slate::bdsbz<R>(slate::Range(range), vl, vu, il, iu, D, E, W, to_opts(no, o));
+        else slate::stebz<R>(slate::Range(range), vl, vu, il, iu, D, E, W, to_opts(no, o));
+        if (nfound) *nfound = int64_t(W.size());
+        if (!W.empty()) {
+            slate_error_if_msg(!w, "stebz / bdsbz: the output array is null");
+            std::copy(W.begin(), W.end(), w);
+        }
+        return 0; }, -1);
+}
+}  // namespace
+
+extern "C" {
+int slate_stebz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t iu, int64_t n, float const* d,
+                    float const* e, int64_t* nfound, float* w, int no, slate_Options const* o) {
+    return bisect_c<float>(false, range, vl, vu, il, iu, n, d, e, nfound, w, no, o);
+}
+int slate_stebz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
+                    double const* e, int64_t* nfound, double* w, int no, slate_Options const* o) {
+    return bisect_c<double>(false, range, vl, vu, il, iu, n, d, e, nfound, w, no, o);
+}
+int slate_bdsbz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t iu, int64_t n, float const* d,
+                    float const* e, int64_t* nfound, float* s, int no, slate_Options const* o) {
+    return bisect_c<float>(true, range, vl, vu, il, iu, n, d, e, nfound, s, no, o);
+}
+int slate_bdsbz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
+                    double const* e, int64_t* nfound, double* s, int no, slate_Options const* o) {
+    return bisect_c<double>(true, range, vl, vu, il, iu, n, d, e, nfound, s, no, o);
+}
+}  // extern "C"

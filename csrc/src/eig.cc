@@ -719,6 +719,43 @@ R range_alpha(R anorm, bool& bad) {
     return R(1);
 }
 
+/// Option::MethodEig / Option::MethodSVD ask for Sturm-count bisection ('b' as
+/// well as 'B', as 'q' is accepted for QR): values only.
+inline bool eig_bisection(Options const& opts) {
+    const int64_t me = get_option<int64_t>(opts, Option::MethodEig, int64_t(MethodEig::DC));
+    return me == int64_t(MethodEig::Bisection) || me == 'b';
+}
+inline bool svd_bisection(Options const& opts) {
+    const int64_t ms = get_option<int64_t>(opts, Option::MethodSVD, int64_t(MethodSVD::QR));
+    return ms == int64_t(MethodSVD::Bisection) || ms == 'b';
+}
+
+/// Eigenvalues of tridiag(d, e) without vectors: sterf, or stebz when
+/// Option::MethodEig is Bisection.
+template <typename R>
+void tridiag_values(std::vector<R>& d, std::vector<R>& e, std::vector<R>& Lambda, Options const& opts) {
+    if (eig_bisection(opts)) {
+        stebz<R>(Range::All, R(0), R(0), 0, 0, d, e, Lambda, opts);
+        return;
+    }
+    trace::Block t2("sterf");
+    host::sterf<R>(int64_t(d.size()), d.data(), e.data());
+    Lambda = d;
+}
+
+/// Singular values of the bidiagonal (d, e) without vectors: the QR
+/// iteration, or bdsbz when Option::MethodSVD is Bisection.
+template <typename R>
+void bidiag_values(std::vector<R>& d, std::vector<R>& e, std::vector<R>& Sigma, Options const& opts) {
+    if (svd_bisection(opts)) {
+        bdsbz<R>(Range::All, R(0), R(0), 0, 0, d, e, Sigma, opts);
+        return;
+    }
+    trace::Block t2("bdsqr");
+    host::bdsqr_core<R>(int64_t(d.size()), d.data(), e.data(), nullptr);
+    Sigma = d;
+}
+
 template <typename R>
 void rescale_values(std::vector<R>& v, R anorm, R alpha) {
     if (alpha == R(1)) return;
@@ -745,9 +782,7 @@ void heev_one_stage(Matrix<R>& F, std::vector<R>& Lambda, Matrix<R>& Z, R anorm,
         hetrd_local<R>(c, n, lf.ptr, lf.ld, d, e, tau.data(), Tfac.data());
     }
     if (!wanted(Z)) {
-        trace::Block t2("sterf");
-        host::sterf<R>(n, d.data(), e.data());
-        Lambda = d;
+        tridiag_values<R>(d, e, Lambda, opts);
         rescale_values(Lambda, anorm, alpha);
         return;
     }
@@ -796,6 +831,9 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
     slate_error_if_msg(mh != int64_t(MethodHetrd::TwoStage) && mh != int64_t(MethodHetrd::OneStage),
                        "heev: Option::MethodHetrd is neither MethodHetrd::TwoStage nor MethodHetrd::OneStage");
     const bool one_stage = mh == int64_t(MethodHetrd::OneStage);
+    if (wanted(Z) && eig_bisection(opts))
+        slate_not_implemented("heev: MethodEig::Bisection computes values only; eigenvectors of the bisection "
+                              "values need inverse iteration, which is not implemented");
     if (one_stage) {
         internal::hetrd_check_operand<T>(A, "heev", "A");
         if (wanted(Z)) internal::hetrd_check_operand<T>(Z, "heev", "Z");
@@ -883,9 +921,7 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
     }
     B.clear(); B.shrink_to_fit();
     if (!wanted(Z)) {
-        trace::Block t2("sterf");
-        host::sterf<R>(n, d.data(), e.data());
-        Lambda = d;
+        tridiag_values<R>(d, e, Lambda, opts);
         rescale_values(Lambda, anorm, alpha);
         return;
     }
@@ -1058,6 +1094,9 @@ void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Ma
 /// and never form a transposed copy of A.
 template <typename T>
 void svd(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Matrix<T>& VT, Options const& opts) {
+    if ((wanted(U) || wanted(VT)) && svd_bisection(opts))
+        slate_not_implemented("svd: MethodSVD::Bisection computes values only; singular vectors of the bisection "
+                              "values need inverse iteration, which is not implemented");
     {
         const int64_t mg = get_option<int64_t>(opts, Option::MethodGebrd, int64_t(MethodGebrd::TwoStage));
         slate_error_if_msg(mg != int64_t(MethodGebrd::TwoStage) && mg != int64_t(MethodGebrd::OneStage),
@@ -1180,9 +1219,7 @@ void svd_one_stage(Matrix<R>& A, std::vector<R>& Sigma, Matrix<R>& U, Matrix<R>&
     }
     const bool wu = wanted(U), wv = wanted(VT);
     if (!wu && !wv) {
-        trace::Block t2("bdsqr");
-        host::bdsqr_core<R>(n, d.data(), e.data(), nullptr);
-        Sigma = d;
+        bidiag_values<R>(d, e, Sigma, opts);
         return;
     }
     const int64_t msvd = get_option<int64_t>(opts, Option::MethodSVD, int64_t(MethodSVD::QR));
@@ -1310,9 +1347,7 @@ void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Ma
     }
     const bool wu = wanted(U), wv = wanted(VT);
     if (!wu && !wv) {
-        trace::Block t2("bdsqr");
-        host::bdsqr_core<R>(n, d.data(), e.data(), nullptr);
-        Sigma = d;
+        bidiag_values<R>(d, e, Sigma, opts);
         return;
     }
     // bdsqr: U2 and Vt = VT2^T in the row layout (rotations mix columns)

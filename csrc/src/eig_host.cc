@@ -2,6 +2,7 @@
 #include "slate_amd/eig_host.hh"
 #include "slate_amd/host_blas.hh"
 #include "slate_amd/secular.hh"
+#include "slate_amd/sturm.hh"
 #include "slate_amd/exception.hh"
 
 #include <algorithm>
@@ -972,8 +973,35 @@ int64_t bdsqr(int64_t n, R* w, R* e, T* U, int64_t ldu, int64_t urows, T* VT, in
 }
 
 //------------------------------------------------------------------------------
+//------------------------------------------------------------------------------
+// Sturm-count bisection: host twins of kernels/stebz.hip (slate_amd/sturm.hh)
+template <typename R>
+void sturm_counts(int64_t n, const R* d, const R* e2, R pivmin, int64_t nx, const R* x, int64_t* cnt) {
+    #pragma omp parallel for schedule(static) if (nx * n > 4096)
+    for (int64_t j = 0; j < nx; ++j) cnt[j] = sturm::count<R>(n, d, e2, x[j], pivmin);
+}
+
+template <typename R>
+int64_t stebz_range(int64_t n, const R* d, const R* e2, R pivmin, R lo, R hi, R abstol, R floor, int64_t k0,
+                    int64_t k1, R* w) {
+    sturm::Interval<R> iv;
+    iv.lo = lo; iv.hi = hi;
+    const sturm::Stop<R> stop{abstol, floor};
+    int64_t most = 0;
+    #pragma omp parallel for schedule(dynamic, 8) reduction(max : most) if ((k1 - k0) * n > 4096)
+    for (int64_t k = k0; k < k1; ++k)
+        most = std::max<int64_t>(most, sturm::bisect<R>(n, d, e2, k, iv, pivmin, stop, w + (k - k0)));
+    return most;
+}
+
+#define SLATE_STEBZ_HOST_INST(R)                                                                        \
+    template void sturm_counts<R>(int64_t, const R*, const R*, R, int64_t, const R*, int64_t*);         \
+    template int64_t stebz_range<R>(int64_t, const R*, const R*, R, R, R, R, R, int64_t, int64_t, R*);
+SLATE_STEBZ_HOST_INST(float)
+SLATE_STEBZ_HOST_INST(double)
+
 #define SLATE_EIGH_INST(T)                                                                              \
-    template struct Reflectors<T>;                                                                      \
+    template struct Reflectors<T>;                                                                     \
     template void hb2st<T>(int64_t, int64_t, T*, int64_t, std::vector<real_type<T>>&,                   \
                            std::vector<real_type<T>>&, Reflectors<T>&, std::vector<T>&);                \
     template void tb2bd<T>(int64_t, int64_t, int64_t, T*, int64_t, std::vector<real_type<T>>&,          \

@@ -58,9 +58,12 @@ struct Params {
     // the getrf family, potrf and the mixed solvers (unset: not passed)
     bool has_gemm_precision = false;
     GemmPrecision gemm_precision = GemmPrecision::Native;
-    // --method-svd qr|dc: Option::MethodSVD of svd
+    // --method-svd qr|dc|bisection: Option::MethodSVD of svd (bisection: of svd_vals too)
     bool has_method_svd = false;
     MethodSVD method_svd = MethodSVD::QR;
+    // --method-eig qr|dc|bisection: Option::MethodEig of heev / heev_vals
+    bool has_method_eig = false;
+    MethodEig method_eig = MethodEig::DC;
     // --method-hetrd two_stage|one_stage: Option::MethodHetrd of heev
     bool has_method_hetrd = false;
     MethodHetrd method_hetrd = MethodHetrd::TwoStage;
@@ -1125,7 +1128,9 @@ Result r_vals(Case<T>& c, int variant) {   // 0 heev values, 1 svd values, 2 heg
             HermitianMatrix<T> A2(Uplo::Lower, Ag2);
             auto Z = c.zeros(c.n, c.n);
             std::vector<R_<T>> L2;
-            heev(A2, L2, Z, c.opts);
+            Options ov = c.opts;   // the vectors path has no bisection: its default method
+            if (get_option<int64_t>(ov, Option::MethodEig, 0) == int64_t(MethodEig::Bisection)) ov.erase(Option::MethodEig);
+            heev(A2, L2, Z, ov);
             double mx = 0;
             for (int64_t i = 0; i < c.n; ++i) mx = std::max(mx, std::abs(double(L[i]) - double(L2[i])));
             r.error = mx / (double(c.n) * c.nrm(A0));
@@ -1190,6 +1195,56 @@ Result r_tridiag(Case<T>& c, int variant) {   // 0 sterf, 1 steqr2, 2 stedc (via
         add(T(-1), ZL, T(1), TZ, c.opts);
         r.error = c.nrm(TZ) / (double(n) * c.nrm(Tm));
     }
+    return r;
+}
+
+/// stebz / bdsbz on the tridiagonal / bidiagonal of r_tridiag, checked against
+/// the count alone (no reference solver): with delta = 16 eps max|T_ij|, value
+/// k (1-based, ascending) must have N(w_k - delta) <= k - 1 and
+/// N(w_k + delta) >= k.  For bdsbz N counts on the Golub-Kahan tridiagonal of
+/// order 2n, whose eigenvalue n + k is the k-th smallest singular value.  The
+/// error is the number of values that miss either bound.
+template <typename T>
+Result r_bisect(Case<T>& c, bool bidiagonal) {
+    using R = R_<T>;
+    const int64_t n = c.n;
+    std::vector<R> d(n), e(std::max<int64_t>(n - 1, 0)), w;
+    for (int64_t i = 0; i < n; ++i) d[i] = R(2) + R(i % 7) / R(10);
+    for (int64_t i = 0; i + 1 < n; ++i) e[i] = R(-1) + R(i % 5) / R(20);
+    Result r;
+    r.time = c.timed([&] {
+        if (bidiagonal) bdsbz<R>(Range::All, R(0), R(0), 0, 0, d, e, w, c.opts);
+        else stebz<R>(Range::All, R(0), R(0), 0, 0, d, e, w, c.opts);
+    });
+    r.flops = 0;
+    if (!c.P.check) return r;
+    if (int64_t(w.size()) != n) { r.error = double(n); return r; }
+    R tmax = 0;
+    for (R v : d) tmax = std::max(tmax, std::abs(v));
+    for (R v : e) tmax = std::max(tmax, std::abs(v));
+    const R delta = R(16) * std::numeric_limits<R>::epsilon() * tmax;
+    std::vector<R> td = d, te = e;
+    int64_t base = 0;   // eigenvalues of the counted matrix below the wanted ones
+    if (bidiagonal) {
+        td.assign(size_t(2 * n), R(0));
+        te.assign(size_t(std::max<int64_t>(2 * n - 1, 0)), R(0));
+        for (int64_t i = 0; i < n; ++i) {
+            te[2 * i] = d[i];
+            if (i + 1 < n) te[2 * i + 1] = e[i];
+        }
+        std::reverse(w.begin(), w.end());   // ascending
+        base = n;
+    }
+    std::vector<R> x(size_t(2 * n));
+    for (int64_t k = 0; k < n; ++k) { x[2 * k] = w[k] - delta; x[2 * k + 1] = w[k] + delta; }
+    const std::vector<int64_t> cnt = sturm_count<R>(td, te, x, c.opts);
+    int64_t bad = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t kk = base + k + 1;
+        bad += !(cnt[2 * k] <= kk - 1 && cnt[2 * k + 1] >= kk);
+        if (k > 0) bad += w[k] < w[k - 1];
+    }
+    r.error = double(bad);
     return r;
 }
 
@@ -1998,6 +2053,8 @@ std::map<std::string, Fn<T>> routines() {
         {"hegv", [](Case<T>& c) { return r_vals<T>(c, 2); }},
         {"sterf", [](Case<T>& c) { return r_tridiag<T>(c, 0); }},
         {"steqr2", [](Case<T>& c) { return r_tridiag<T>(c, 1); }},
+        {"stebz", [](Case<T>& c) { return r_bisect<T>(c, false); }},
+        {"bdsbz", [](Case<T>& c) { return r_bisect<T>(c, true); }},
         {"add", [](Case<T>& c) { return r_aux<T>(c, 0); }},
         {"copy", [](Case<T>& c) { return r_aux<T>(c, 1); }},
         {"scale", [](Case<T>& c) { return r_aux<T>(c, 2); }},
@@ -2080,8 +2137,13 @@ int run_type(Params const& P, char tc, std::string const& name) {
                     "posv_mixed", "posv_mixed_gmres"};
                 const bool with_precision = P.has_gemm_precision && takes_precision.count(name) > 0;
                 if (with_precision) c.opts[Option::GemmPrecision] = P.gemm_precision;
-                const bool with_method_svd = P.has_method_svd && name == "svd";
+                const bool with_method_svd =
+                    P.has_method_svd &&
+                    (name == "svd" || (name == "svd_vals" && P.method_svd == MethodSVD::Bisection));
                 if (with_method_svd) c.opts[Option::MethodSVD] = P.method_svd;
+                const bool with_method_eig =
+                    P.has_method_eig && (name == "heev" || name == "heev_vals");
+                if (with_method_eig) c.opts[Option::MethodEig] = P.method_eig;
                 const bool with_method_hetrd = P.has_method_hetrd && name == "heev";
                 if (with_method_hetrd) c.opts[Option::MethodHetrd] = P.method_hetrd;
                 const bool with_method_gebrd = P.has_method_gebrd && (name == "svd" || name == "svd_vals");
@@ -2107,7 +2169,15 @@ int run_type(Params const& P, char tc, std::string const& name) {
                     double gf = (r.time > 0 && r.flops > 0) ? r.flops / r.time / 1e9 : NAN;
                     const std::string prec =
                         (with_precision ? std::string("  gemm_precision=") + to_string(P.gemm_precision) : "") +
-                        (with_method_svd ? std::string("  method_svd=") + (P.method_svd == MethodSVD::DC ? "dc" : "qr")
+                        (with_method_svd ? std::string("  method_svd=") +
+                                               (P.method_svd == MethodSVD::DC          ? "dc"
+                                                : P.method_svd == MethodSVD::Bisection ? "bisection"
+                                                                                       : "qr")
+                                         : "") +
+                        (with_method_eig ? std::string("  method_eig=") +
+                                               (P.method_eig == MethodEig::QR          ? "qr"
+                                                : P.method_eig == MethodEig::Bisection ? "bisection"
+                                                                                       : "dc")
                                          : "") +
                         (with_method_hetrd ? std::string("  method_hetrd=") +
                                                  (P.method_hetrd == MethodHetrd::OneStage ? "one_stage" : "two_stage")
@@ -2145,7 +2215,8 @@ void usage() {
         "       [--timer-level 1|2] [--itermax N] [--fallback y|n] [--pivot-threshold X]\n"
         "       [--uplo l|u] [--trans n|t|c] [--side l|r] [--diag n|u] [--cond C] [--ib IB]\n"
         "       [--nonuniform-nb y|n] [--go c|r] [--do r|c]\n"
-        "       [--gemm-precision native|bf16|bf16x3|bf16x6] [--method-svd qr|dc]\n"
+        "       [--gemm-precision native|bf16|bf16x3|bf16x6] [--method-svd qr|dc|bisection]\n"
+        "       [--method-eig qr|dc|bisection]\n"
         "       [--method-hetrd two_stage|one_stage] [--method-gebrd two_stage|one_stage]\n"
         "routines:");
     for (auto const& kv : routines<double>()) std::printf(" %s", kv.first.c_str());
@@ -2210,9 +2281,20 @@ int main(int argc, char** argv) {
         else if (a == "--method-svd") {
             std::string v = val();
             for (auto& ch : v) ch = char(std::tolower((unsigned char)ch));
-            if (v != "qr" && v != "dc") { std::fprintf(stderr, "--method-svd: qr or dc\n"); usage(); return 2; }
-            P.method_svd = v == "dc" ? MethodSVD::DC : MethodSVD::QR;
+            if (v != "qr" && v != "dc" && v != "bisection") {
+                std::fprintf(stderr, "--method-svd: qr, dc or bisection\n"); usage(); return 2;
+            }
+            P.method_svd = v == "dc" ? MethodSVD::DC : (v == "bisection" ? MethodSVD::Bisection : MethodSVD::QR);
             P.has_method_svd = true;
+        }
+        else if (a == "--method-eig") {
+            std::string v = val();
+            for (auto& ch : v) ch = char(std::tolower((unsigned char)ch));
+            if (v != "qr" && v != "dc" && v != "bisection") {
+                std::fprintf(stderr, "--method-eig: qr, dc or bisection\n"); usage(); return 2;
+            }
+            P.method_eig = v == "qr" ? MethodEig::QR : (v == "bisection" ? MethodEig::Bisection : MethodEig::DC);
+            P.has_method_eig = true;
         }
         else if (a == "--method-hetrd") {
             std::string v = val();

@@ -18,7 +18,7 @@ except Exception:  # torch is optional for the native library
     _torch = None
 from . import _slate
 from ._core import (Target, Op, Uplo, Diag, Side, Norm, GridOrder, Layout, Equed, Grid, Job, MethodSVD,  # noqa: F401
-                    MethodHetrd, MethodGebrd, Vect,
+                    MethodHetrd, MethodGebrd, Vect, MethodEig, Range,
                     Matrix, HermitianMatrix, SymmetricMatrix, TriangularMatrix, TrapezoidMatrix,
                     BandMatrix, TriangularBandMatrix, HermitianBandMatrix, general, band_matrix,
                     hermitian_band_matrix,

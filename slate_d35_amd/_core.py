@@ -15,6 +15,8 @@ Op = _slate.Op
 Uplo = _slate.Uplo
 Job = _slate.Job
 MethodSVD = _slate.MethodSVD
+MethodEig = _slate.MethodEig
+Range = _slate.Range
 MethodHetrd = _slate.MethodHetrd
 MethodGebrd = _slate.MethodGebrd
 Vect = _slate.Vect

@@ -6,12 +6,13 @@ from ._wrap import call
 __all__ = ["heev", "hegv", "hegst", "svd", "svd_vals", "gesvd", "eig", "eig_vals", "he2hb", "hb2st", "sterf",
            "steqr", "stedc", "ge2tb", "tb2bd", "bdsqr", "syev", "sygv", "hb2st_band", "unmtr_hb2st",
            "unmtr_he2hb", "tb2bd_band", "unmbr_tb2bd", "unmbr_ge2tb", "steqr2", "stedc_matrix", "bdsqr_matrix",
-           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd", "gebrd", "unmbr_gebrd"]
+           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd", "gebrd", "unmbr_gebrd", "stebz", "bdsbz"]
 
 
 def heev(A, Z=None, target=None, **kw):
     """Eigenvalues (ascending numpy array; vectors into Z if given) of a
-    Hermitian matrix.  method_eig="dc" (divide and conquer, default) or "qr"."""
+    Hermitian matrix.  method_eig="dc" (divide and conquer, default) or "qr";
+    "bisection" (values only, Z None): stebz in place of sterf."""
     import numpy as np
     return np.asarray(call("heev", A, A, Z, target=target, **kw))
 
@@ -30,7 +31,8 @@ def hegst(itype, A, B, target=None, **kw):
 def svd(A, U=None, VT=None, target=None, **kw):
     """Singular values (descending numpy array); thin U (m x k) and VT
     (k x n), k = min(m, n), filled when given.  method_svd="qr" (bidiagonal
-    QR iteration, default) or "dc" (divide and conquer, bdsdc).
+    QR iteration, default) or "dc" (divide and conquer, bdsdc); "bisection"
+    (values only, U and VT None): bdsbz in place of the QR iteration.
     method_gebrd="two_stage" (ge2tb + tb2bd, default) or "one_stage" (gebrd:
     real types, one process), also for svd_vals and gesvd."""
     import numpy as np
@@ -63,6 +65,50 @@ def hb2st(a, kd):
 def sterf(d, e, **kw):
     from .. import _slate
     return _slate.sterf(list(d), list(e))
+
+
+def _bisect(bidiagonal, d, e, range, vl, vu, il, iu, target, kw):
+    import numpy as np
+    from .. import _slate
+    from .._core import Range, opts
+    d = np.asarray(d)
+    e = np.asarray(e)
+    dt = np.result_type(d.dtype, e.dtype) if e.size else d.dtype
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        dt = np.dtype(np.float64)
+    if not isinstance(range, Range):
+        try:
+            range = {"all": Range.All, "a": Range.All, "value": Range.Value, "v": Range.Value,
+                     "index": Range.Index, "i": Range.Index}[str(range).lower()]
+        except KeyError:
+            raise ValueError(f"range: \"all\", \"value\" or \"index\", not {range!r}") from None
+    if range == Range.Value and (vl is None or vu is None):
+        raise ValueError("range=\"value\" needs vl and vu")
+    if range == Range.Index and (il is None or iu is None):
+        raise ValueError("range=\"index\" needs il and iu")
+    return _slate.stebz("s" if dt == np.float32 else "d", bidiagonal, range,
+                        float(0 if vl is None else vl), float(0 if vu is None else vu),
+                        int(0 if il is None else il), int(0 if iu is None else iu),
+                        d.astype(np.float64).tolist(), e.astype(np.float64).tolist(), opts(target, **kw))
+
+
+def stebz(d, e, range="all", vl=None, vu=None, il=None, iu=None, target=None, **kw):
+    """Eigenvalues (ascending ndarray of d's precision) of the symmetric
+    tridiagonal (d, e) by Sturm-count bisection.  range="all"; "index": the
+    1-based il <= k <= iu of the ascending order; "value": those in [vl, vu).
+    A subset has the bits of the same entries of the full result.  target="d"
+    runs the gfx950 kernel (one launch, one host synchronisation), the host
+    targets the same arithmetic with OpenMP across eigenvalues.  float32 and
+    float64.  Raises on non-finite entries, vl >= vu or il / iu out of range."""
+    return _bisect(False, d, e, range, vl, vu, il, iu, target, kw)
+
+
+def bdsbz(d, e, range="all", vl=None, vu=None, il=None, iu=None, target=None, **kw):
+    """Singular values (descending ndarray) of the upper bidiagonal (d, e) by
+    bisection on its Golub-Kahan tridiagonal: high relative accuracy down to
+    sqrt(safe_min) max|B|.  "index" counts from the largest (il = 1); the
+    signs of d and e do not matter.  Arguments as for stebz."""
+    return _bisect(True, d, e, range, vl, vu, il, iu, target, kw)
 
 
 def steqr(d, e, Z=None, **kw):

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "gemv_t_block", "gemv_n_block", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "gemv_t_block", "gemv_n_block", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -82,6 +82,31 @@ def bdsdc_stats() -> dict:
     (in all and per tree level, root first) and the launches of the three
     device kernels (zero on the host target)."""
     return _slate.bdsdc_stats()
+
+
+def sturm_count(d, e, x, target=None):
+    """N(x_j), the number of eigenvalues of the symmetric tridiagonal (d, e)
+    below each shift x_j (int64 ndarray): the raw count kernel that stebz and
+    bdsbz refine with, one lane per shift on target="d", the same recurrence
+    (csrc/include/slate_amd/sturm.hh) on the host targets.  float32 / float64
+    after d."""
+    import numpy as np
+    from .._core import opts
+    d = np.asarray(d)
+    t = "s" if d.dtype == np.float32 else "d"
+    as_list = lambda a: np.asarray(a).astype(np.float64).ravel().tolist()
+    return _slate.sturm_count(t, as_list(d), as_list(e), as_list(x), opts(target))
+
+
+def stebz_stats() -> dict:
+    """Counters of the last stebz / bdsbz of this process (also through heev /
+    svd_vals with method_eig / method_svd "bisection"): `n` the order of the
+    tridiagonal counted on (2n for bdsbz), `values` returned, `points` P per
+    eigenvalue and step (1 on the host; chosen from n and the device's CU
+    count, SLATE_STEBZ_POINTS overrides), `steps` the most any value took,
+    `launches` (1, or 2 for a range by value; 0 on the host) and `host_syncs`
+    (1 on the device)."""
+    return _slate.stebz_stats()
 
 
 def hetrd_stats() -> dict:

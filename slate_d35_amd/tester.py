@@ -79,7 +79,11 @@ class Ctx:
 
     def method_svd(self):
         ms = getattr(self.a, "method_svd", None)
-        return ms if ms and self.name == "svd" else None
+        return ms if ms and (self.name == "svd" or (self.name == "svd_vals" and ms == "bisection")) else None
+
+    def method_eig(self):
+        me = getattr(self.a, "method_eig", None)
+        return me if me and self.name in ("heev", "heev_vals") else None
 
     def method_hetrd(self):
         mh = getattr(self.a, "method_hetrd", None)
@@ -99,6 +103,8 @@ class Ctx:
             o["gemm_precision"] = self.gemm_precision()
         if self.method_svd():
             o["method_svd"] = self.method_svd()
+        if self.method_eig():
+            o["method_eig"] = self.method_eig()
         return o
 
 
@@ -371,6 +377,66 @@ def r_svd(c):
     return t, err
 
 
+def r_heev_vals(c):
+    a, A = _sym(c)
+    t, w = _timed(lambda: M.heev(core.HermitianMatrix(core.Uplo.Lower, A), None, **c.opts()))
+    err = None
+    if c.a.check:
+        ref = np.linalg.eigvalsh(a.astype(np.complex128 if np.iscomplexobj(a) else np.float64))
+        err = np.abs(w - ref).max() / (max(np.abs(ref).max(), 1e-300) * c.n)
+    return t, err
+
+
+def r_svd_vals(c):
+    a, A = c.mat(c.m, c.n)
+    t, sv = _timed(lambda: M.svd_vals(A, **c.opts()))
+    err = None
+    if c.a.check:
+        ref = np.linalg.svd(a.astype(np.complex128 if np.iscomplexobj(a) else np.float64), compute_uv=False)
+        err = np.abs(sv - ref).max() / (ref.max() * max(c.m, c.n))
+    return t, err
+
+
+def _bisect(c, bidiagonal):
+    """stebz / bdsbz checked against the count alone: with delta = 16 eps
+    max|T_ij|, value k (1-based, ascending) must have N(w_k - delta) <= k - 1
+    and N(w_k + delta) >= k; for bdsbz N counts on the Golub-Kahan tridiagonal
+    of order 2n.  The error is the number of values that miss a bound."""
+    _real_only(c)
+    n = c.n
+    i = np.arange(n)
+    d = (2 + (i % 7) / 10).astype(c.dt)
+    e = (-1 + (i[:max(n - 1, 0)] % 5) / 20).astype(c.dt)
+    fn = M.bdsbz if bidiagonal else M.stebz
+    t, w = _timed(lambda: fn(d, e, target=c.target))
+    if not c.a.check:
+        return t, None
+    if w.shape != (n,):
+        return t, float(n)
+    delta = c.dt(16) * np.finfo(c.dt).eps * max(np.abs(d).max(), np.abs(e).max() if e.size else 0)
+    td, te, base = d, e, 0
+    if bidiagonal:
+        td = np.zeros(2 * n, c.dt)
+        te = np.zeros(max(2 * n - 1, 0), c.dt)
+        te[0::2] = d
+        te[1::2] = e
+        w, base = w[::-1], n
+    from . import ops
+    lo = ops.sturm_count(td, te, (w - delta).astype(c.dt), target=c.target)
+    hi = ops.sturm_count(td, te, (w + delta).astype(c.dt), target=c.target)
+    kk = base + 1 + np.arange(n)
+    bad = int(np.sum(~((lo <= kk - 1) & (hi >= kk)))) + int(np.sum(np.diff(w) < 0))
+    return t, float(bad)
+
+
+def r_stebz(c):
+    return _bisect(c, False)
+
+
+def r_bdsbz(c):
+    return _bisect(c, True)
+
+
 def r_hesv(c):
     a, A = c.mat(c.n, c.n)
     a = (a + a.conj().T) / 2
@@ -433,6 +499,10 @@ ROUTINES = {
     "geqrf": (r_geqrf, lambda m, n, k: F.geqrf_flops(m, n)),
     "gels": (r_gels, lambda m, n, k: F.geqrf_flops(m, n)),
     "heev": (r_heev, lambda m, n, k: 4.0 / 3.0 * n ** 3),
+    "heev_vals": (r_heev_vals, lambda m, n, k: 4.0 / 3.0 * n ** 3),
+    "svd_vals": (r_svd_vals, lambda m, n, k: 8.0 / 3.0 * n ** 3),
+    "stebz": (r_stebz, lambda m, n, k: 0.0),
+    "bdsbz": (r_bdsbz, lambda m, n, k: 0.0),
     "hetrd": (r_hetrd, lambda m, n, k: 4.0 / 3.0 * n ** 3),
     "unmtr_hetrd": (r_unmtr_hetrd, lambda m, n, k: 0.0),
     "gebrd": (r_gebrd, lambda m, n, k: 4.0 * m * n * n - 4.0 / 3.0 * n ** 3),
@@ -461,8 +531,11 @@ def main(argv=None):
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--gemm-precision", default=None, choices=["native", "bf16", "bf16x3", "bf16x6"],
                     help="arithmetic of the fp32 trailing updates of gemm, getrf*, potrf and the mixed solvers")
-    ap.add_argument("--method-svd", default=None, choices=["qr", "dc"],
-                    help="bidiagonal stage of svd: QR iteration (default) or divide and conquer")
+    ap.add_argument("--method-svd", default=None, choices=["qr", "dc", "bisection"],
+                    help="bidiagonal stage of svd: QR iteration (default) or divide and conquer; "
+                         "bisection: of svd_vals (values only)")
+    ap.add_argument("--method-eig", default=None, choices=["qr", "dc", "bisection"],
+                    help="tridiagonal stage of heev / heev_vals; bisection: values only")
     ap.add_argument("--method-hetrd", default=None, choices=["two_stage", "one_stage"],
                     help="tridiagonal reduction of heev: two stages (default) or the one-stage hetrd")
     ap.add_argument("--method-gebrd", default=None, choices=["two_stage", "one_stage"],
@@ -507,6 +580,7 @@ def main(argv=None):
                                   f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}"
                                   + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else "")
                                   + (f"  method_svd={c.method_svd()}" if c.method_svd() else "")
+                                  + (f"  method_eig={c.method_eig()}" if c.method_eig() else "")
                                   + (f"  method_hetrd={c.method_hetrd()}" if c.method_hetrd() else "")
                                   + (f"  method_gebrd={c.method_gebrd()}" if c.method_gebrd() else ""),
                                   flush=True)
