@@ -222,6 +222,27 @@ int slate_bdsbz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t i
 int slate_bdsbz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
                     double const* e, int64_t* nfound, double* s, int nopts, slate_Options const* opts);
 
+/* QR with column pivoting, real types (slate::geqp3 / unmqr_geqp3 / gelsy).
+ * jpvt has room for n entries and is 0-based: column j of A P is column
+ * jpvt[j] of the input.  least_squares_solve_rank: BX is max(m, n) x nrhs, its
+ * first n rows receive the minimum-norm solution for the numerical rank that
+ * rcond selects (|R_kk| > rcond |R_00|), which *rank receives.  Returns 0, or
+ * -1 (slate_last_error). */
+int slate_qr_factor_pivoted_r32(slate_Matrix_r32 A, int64_t* jpvt, slate_TriangularFactors_r32 T, int nopts,
+                                slate_Options const* opts);
+int slate_qr_factor_pivoted_r64(slate_Matrix_r64 A, int64_t* jpvt, slate_TriangularFactors_r64 T, int nopts,
+                                slate_Options const* opts);
+int slate_qr_pivoted_multiply_by_q_r32(slate_Side side, slate_Op op, slate_Matrix_r32 A,
+                                       slate_TriangularFactors_r32 T, slate_Matrix_r32 C, int nopts,
+                                       slate_Options const* opts);
+int slate_qr_pivoted_multiply_by_q_r64(slate_Side side, slate_Op op, slate_Matrix_r64 A,
+                                       slate_TriangularFactors_r64 T, slate_Matrix_r64 C, int nopts,
+                                       slate_Options const* opts);
+int slate_least_squares_solve_rank_r32(slate_Matrix_r32 A, slate_Matrix_r32 BX, float rcond, int64_t* rank,
+                                       int nopts, slate_Options const* opts);
+int slate_least_squares_solve_rank_r64(slate_Matrix_r64 A, slate_Matrix_r64 BX, double rcond, int64_t* rank,
+                                       int nopts, slate_Options const* opts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,5 +165,15 @@ void hetrd(int64_t n, R* A, int64_t lda, R* d, R* e, R* tau, int64_t nb);
 template <typename R>
 void gebrd(int64_t m, int64_t n, R* A, int64_t lda, R* d, R* e, R* tauq, R* taup, int64_t nb);
 
+/// QR with column pivoting of a real m x n A (LAPACK geqp3, laqps panels of nb
+/// columns): A P = Q R, column j of A P being column jpvt[j] (0-based, n
+/// entries) of the input; R in the upper triangle / trapezoid, Q = H_0 ..
+/// H_{k-1}, k = min(m, n), H_j = I - tau_j v_j v_j^T with v_j below the
+/// diagonal of column j, unit entry implied.  A column whose downdated norm
+/// cannot be trusted has its norm recomputed inside the panel; the number of
+/// such columns returns.
+template <typename R>
+int64_t geqp3(int64_t m, int64_t n, R* A, int64_t lda, int64_t* jpvt, R* tau, int64_t nb);
+
 }  // namespace host
 }  // namespace slate

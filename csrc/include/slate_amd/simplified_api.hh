@@ -256,6 +256,20 @@ void qr_multiply_by_q(Side side, Op op, Matrix<T>& A, TriangularFactors<T>& T_, 
                       Options const& opts = {}) {
     unmqr(side, op, A, T_, C, opts);
 }
+/// QR with column pivoting (geqp3 / unmqr_geqp3 / gelsy); jpvt is 0-based.
+template <typename T>
+void qr_factor_pivoted(Matrix<T>& A, std::vector<int64_t>& jpvt, TriangularFactors<T>& T_, Options const& opts = {}) {
+    geqp3(A, jpvt, T_, opts);
+}
+template <typename T>
+void qr_pivoted_multiply_by_q(Side side, Op op, Matrix<T>& A, TriangularFactors<T>& T_, Matrix<T>& C,
+                              Options const& opts = {}) {
+    unmqr_geqp3(side, op, A, T_, C, opts);
+}
+template <typename T>
+int64_t least_squares_solve_rank(Matrix<T>& A, Matrix<T>& BX, real_type<T> rcond, Options const& opts = {}) {
+    return gelsy(A, BX, rcond, opts);
+}
 template <typename T>
 void lq_factor(Matrix<T>& A, TriangularFactors<T>& T_, Options const& opts = {}) {
     gelqf(A, T_, opts);

@@ -475,6 +475,50 @@ struct GebrdStats {
 };
 GebrdStats gebrd_stats();
 
+/// QR with column pivoting (src/geqp3.cc; LAPACK geqp3): A P = Q R with
+/// |R_kk| non-increasing.  Real types, any m and n, a matrix of one process on
+/// one device or the host; anything else throws NotImplemented.  R is left in
+/// the upper triangle / trapezoid of A, the k = min(m, n) reflectors below the
+/// diagonal with their unit entries implied, as geqrf leaves them.  jpvt gets
+/// n entries, 0-based: column j of A P is column jpvt[j] of the input; all
+/// columns are free and the entry value of jpvt is ignored.  T[0] holds the
+/// 64 x 64 block-reflector factor of every panel of 64 columns (panel p at
+/// column 64 p), T[1] the scalars tau.  The entries of A are assumed to be such
+/// that their squares neither overflow nor underflow (gelsy scales first).
+template <typename T>
+void geqp3(Matrix<T>& A, std::vector<int64_t>& jpvt, TriangularFactors<T>& T_, Options const& opts = {});
+/// C := op(Q) C (Side::Left) or C op(Q) (Side::Right), Q = H_0 .. H_{k-1} of
+/// order m from geqp3(A, jpvt, T): one larfb per panel.
+template <typename T>
+void unmqr_geqp3(Side side, Op op, Matrix<T>& A, TriangularFactors<T>& T_, Matrix<T>& C, Options const& opts = {});
+/// Minimum-norm least-squares solution for a numerical rank chosen by rcond
+/// (LAPACK gelsy's contract with a simpler rank rule): geqp3, the rank r = the
+/// number of leading k with |R_kk| > rcond |R_00| (the plain diagonal rule, not
+/// LAPACK's incremental condition estimate), C = (Q^T B)(0:r), the minimum-norm
+/// solution of [R11 R12] y = C by an LQ factorization of that row block, and
+/// X = P y.  BX is max(m, n) x nrhs with B in its first m rows; on exit its
+/// first n rows hold X.  A is overwritten by its factorization (scaled into
+/// range first when its largest entry is tiny or huge).  r returns; r = 0
+/// gives X = 0.  Operands as for geqp3.
+template <typename T>
+int64_t gelsy(Matrix<T>& A, Matrix<T>& BX, real_type<T> rcond, Options const& opts = {});
+/// Counters of the last geqp3 of this process (also through gelsy): factored
+/// columns, panels, launches of each kernel kind (zero on the host target),
+/// the columns whose norm was recomputed inside a panel (counted on the device
+/// and fetched with the final copy) and host synchronisations inside the
+/// factorization.  With SLATE_GEQP3_PROFILE=1 in the environment the device
+/// factorization also records events between its kernels and reports the
+/// device milliseconds of the pivot search and swap, the product A^T v, the
+/// other column kernels (panel), the trailing GEMMs and the T factors; zero
+/// otherwise.
+struct Geqp3Stats {
+    int64_t columns = 0, panels = 0, host_syncs = 0, norm_recomputes = 0;
+    int64_t launches_norms = 0, launches_pivot = 0, launches_swap = 0, launches_column = 0, launches_larfg = 0,
+            launches_product = 0, launches_finish = 0, launches_recompute = 0;
+    double ms_pivot = 0, ms_product = 0, ms_panel = 0, ms_gemm = 0, ms_larft = 0;
+};
+Geqp3Stats geqp3_stats();
+
 //------------------------------------------------------------------------------
 // Real-symmetric aliases (real types only) and compatibility names.
 template <typename T>

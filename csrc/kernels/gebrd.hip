@@ -32,6 +32,7 @@
 // them once through LDS; pass 2 (A v) writes each tile's row sums per block
 // column.  Loads outside the block are masked: nothing outside it is read.
 #include "device_common.hh"
+#include "gemv_tiles.hh"
 #include "kernels.hh"
 
 #include <algorithm>
@@ -41,97 +42,7 @@ namespace dev {
 
 namespace {
 
-constexpr int GT = 256;    // threads of every kernel here
-constexpr int TR = 64;     // tile rows = lanes
-constexpr int TC = 16;     // tile columns
-constexpr int GR = 64;     // rows (columns) per workgroup of the finishing kernels
-
-// block sum, the same bits in every thread; all threads of the block call it
-template <typename R>
-__device__ inline R gb_block_sum(R v, R* sh) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// sum over the 4 waves of each lane's value, the same bits in all of them
-template <typename R>
-__device__ inline R gb_waves_sum(R v, R (*red)[GR]) {
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    __syncthreads();
-    red[g][lane] = v;
-    __syncthreads();
-    return (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-}
-
-// sum of cnt workgroup partials, the same bits in every thread of every workgroup
-template <typename R>
-__device__ inline R gb_partial_sum(const R* p, int cnt, R* sh) {
-    R s = R(0);
-    for (int q = threadIdx.x; q < cnt; q += GT) s += p[q];
-    return gb_block_sum<R>(s, sh);
-}
-
-// larfg from alpha and the sum of squares of the tail
-template <typename R>
-__device__ inline void gb_larfg(R alpha, R ss, R& beta, R& tau, R& scale) {
-    beta = alpha; tau = R(0); scale = R(0);
-    if (ss != R(0)) {
-        const R nrm = sqrt(alpha * alpha + ss);
-        beta = alpha >= R(0) ? -nrm : nrm;
-        tau = (beta - alpha) / beta;
-        scale = R(1) / (alpha - beta);
-    }
-}
-
-// one workgroup of A^T x over the mr x nc block at A: block column J, chunk k.
-// colpart[k * nc + j] = sum over the chunk's rows of A(r, j) x(r)
-template <typename R>
-__device__ inline void gemv_t_tiles(int64_t mr, int64_t nc, const R* A, int64_t lda, const R* x, R* colpart, int tpw,
-                                    int64_t k, int64_t J, R* cbuf) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t c0 = J * TC;
-    const int ncol = int(min(int64_t(TC), nc - c0));
-    const int64_t nRT = (mr + TR - 1) / TR;
-    const int64_t tbase = k * (4 * tpw);
-    R cacc[TC];
-    #pragma unroll
-    for (int c = 0; c < TC; ++c) cacc[c] = R(0);
-    for (int s = 0; s < tpw; ++s) {
-        const int64_t t = tbase + w + 4 * s;
-        if (t >= nRT) break;    // uniform over the wave
-        const int64_t r = t * TR + lane;
-        const bool inb = r < mr;
-        const R* ap = A + r + c0 * lda;
-        const R xr = inb ? x[r] : R(0);
-        #pragma unroll
-        for (int c = 0; c < TC; ++c) {
-            // a masked lane loads x[0] instead (a valid address) and drops it: no branch per load
-            const bool ok = inb && c < ncol;
-            const R ld = *(ok ? ap + c * lda : x);
-            cacc[c] += ok ? ld * xr : R(0);
-        }
-    }
-    // lanes -> LDS, one thread per (wave, column) sums the 64 lanes in order into slot 64 of its
-    // row (not read by anyone before the next barrier), then the 4 waves
-    #pragma unroll
-    for (int c = 0; c < TC; ++c) cbuf[(w * TC + c) * 65 + lane] = cacc[c];
-    __syncthreads();
-    if (threadIdx.x < 4 * TC) {
-        const R* q = cbuf + threadIdx.x * 65;
-        R v = R(0);
-        for (int l = 0; l < 64; ++l) v += q[l];
-        cbuf[threadIdx.x * 65 + 64] = v;
-    }
-    __syncthreads();
-    if (int(threadIdx.x) < ncol) {
-        const int c = threadIdx.x;
-        colpart[k * nc + c0 + c] = (cbuf[(0 * TC + c) * 65 + 64] + cbuf[(1 * TC + c) * 65 + 64]) +
-                                   (cbuf[(2 * TC + c) * 65 + 64] + cbuf[(3 * TC + c) * 65 + 64]);
-    }
-}
+// GT, TR, TC, GR, the gb_* reductions, gb_larfg and gemv_t_tiles (A^T x): gemv_tiles.hh
 
 // one workgroup of A x over the mr x nc block at A: block column J, chunk k.
 // rowpart[J * mr + r] = sum over the block column of A(r, j) x(j).  The wave's
@@ -454,9 +365,6 @@ __global__ __launch_bounds__(GT) void gebrd_form_vt_kernel(int64_t nv, int kb, c
     if (j >= nv) return;
     out[j + int64_t(k) * ldo] = j < k ? R(0) : (j == k ? R(1) : Arow[k + j * lda]);
 }
-
-inline unsigned gblocks_of(int64_t rows) { return unsigned((rows + GT - 1) / GT); }
-inline unsigned grblocks_of(int64_t rows) { return unsigned((rows + GR - 1) / GR); }
 
 }  // namespace
 

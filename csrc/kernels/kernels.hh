@@ -294,6 +294,50 @@ void gebrd_finish_x(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int
 template <typename R>
 void gebrd_form_vt(int64_t nv, int kb, const R* Arow, int64_t lda, R* out, int64_t ldo, hipStream_t s);
 
+// ---- QR with column pivoting (geqp3.hip), float and double
+/// device vectors of the factorization of an m x n matrix with panels of 64 columns
+template <typename R>
+struct Geqp3Work {
+    R* F = nullptr;                          // n x 64, leading dimension ldf
+    int64_t ldf = 0;
+    R *vn1 = nullptr, *vn2 = nullptr;        // n each: partial and reference column norms
+    R* v = nullptr;                          // m: the current reflector
+    R* tau = nullptr;                        // min(m, n)
+    R* scal = nullptr;                       // 1: alpha of the current column
+    R* ssq = nullptr;                        // ceil(m / 64): partial sums of squares
+    R* pdots = nullptr;                      // ceil(m / 256) x 64: partials of V^T v
+    R* colpart = nullptr;                    // product partials: (m / 256 + 2) n
+    int64_t *jpvt = nullptr, *recomputes = nullptr;   // n each, contiguous: one copy fetches both
+    int64_t* piv = nullptr;                  // 1: the pivot column of the current step
+    int* flag = nullptr;                     // n: the downdated norm of the column is not trusted
+    R tol3z = R(0);                          // sqrt of the relative machine precision
+};
+/// column norms into vn1 = vn2, jpvt = identity, counters and flags cleared
+template <typename R>
+void geqp3_norms(int64_t m, int64_t n, const R* A, int64_t lda, Geqp3Work<R> const& wk, hipStream_t s);
+/// the seven launches of column j of the panel that starts at j0 (see geqp3.hip)
+template <typename R>
+void geqp3_pivot(int64_t n, int64_t j, Geqp3Work<R> const& wk, hipStream_t s);
+template <typename R>
+void geqp3_swap(int64_t m, int64_t j, int64_t j0, R* A, int64_t lda, Geqp3Work<R> const& wk, hipStream_t s);
+template <typename R>
+void geqp3_column(int64_t m, int64_t j, int64_t j0, R* A, int64_t lda, Geqp3Work<R> const& wk, hipStream_t s);
+template <typename R>
+void geqp3_larfg(int64_t m, int64_t j, R* A, int64_t lda, Geqp3Work<R> const& wk, hipStream_t s);
+template <typename R>
+void geqp3_product(int64_t m, int64_t n, int64_t j, int64_t j0, const R* A, int64_t lda, Geqp3Work<R> const& wk,
+                   hipStream_t s);
+template <typename R>
+void geqp3_finish(int64_t m, int64_t n, int64_t j, int64_t j0, R* A, int64_t lda, Geqp3Work<R> const& wk,
+                  hipStream_t s);
+template <typename R>
+void geqp3_recompute(int64_t m, int64_t n, int64_t j, int64_t j0, R* A, int64_t lda, Geqp3Work<R> const& wk,
+                     hipStream_t s);
+/// X(jpvt[i], :) = Y(i, :) for i < n (gelsy's X = P y); X and Y do not overlap
+template <typename R>
+void geqp3_scatter_rows(int64_t n, int64_t nrhs, const int64_t* jpvt, const R* Y, int64_t ldy, R* X, int64_t ldx,
+                        hipStream_t s);
+
 // ---- eigensolver back-transform (eig.hip)
 /// G (k x k Gram V^H V) -> T^{-1} = striu(G) + diag(1 / tau) in place.
 /// Stage-2 back-transform (hb2st_apply.hip), fp64.  ng groups of 64

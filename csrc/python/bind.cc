@@ -632,6 +632,28 @@ PYBIND11_MODULE(_slate, m) {
         r["ms_larft"] = st.ms_larft;
         return r;
     });
+    m.def("geqp3_stats", []() {
+        const Geqp3Stats st = geqp3_stats();
+        py::dict r;
+        r["columns"] = st.columns;
+        r["panels"] = st.panels;
+        r["host_syncs"] = st.host_syncs;
+        r["norm_recomputes"] = st.norm_recomputes;
+        r["launches_norms"] = st.launches_norms;
+        r["launches_pivot"] = st.launches_pivot;
+        r["launches_swap"] = st.launches_swap;
+        r["launches_column"] = st.launches_column;
+        r["launches_larfg"] = st.launches_larfg;
+        r["launches_product"] = st.launches_product;
+        r["launches_finish"] = st.launches_finish;
+        r["launches_recompute"] = st.launches_recompute;
+        r["ms_pivot"] = st.ms_pivot;
+        r["ms_product"] = st.ms_product;
+        r["ms_panel"] = st.ms_panel;
+        r["ms_gemm"] = st.ms_gemm;
+        r["ms_larft"] = st.ms_larft;
+        return r;
+    });
     // y = A^T x (trans) or A x over the mr x nc block at A (device pointers); use_lb: through
     // lb::gemv instead of the block kernels (the yardstick)
     // (repeat: the product is enqueued that many times before the one synchronisation, for timing)

@@ -348,6 +348,14 @@ void bind_drivers(py::module_& m, std::string const& s) {
         return py::make_tuple(D, E, TQ, TP); });
     DEF("unmbr_gebrd", [](Vect vt, Side sd, Op op_, Matrix<T>& A, TriangularFactors<T> Tf, Matrix<T>& C, py::dict o) {
         Options op = to_options(o); py::gil_scoped_release r; unmbr_gebrd(vt, sd, op_, A, Tf, C, op); });
+    DEF("geqp3", [](Matrix<T>& A, py::dict o) {
+        Options op = to_options(o); std::vector<int64_t> jpvt; TriangularFactors<T> Tf;
+        { py::gil_scoped_release r; geqp3(A, jpvt, Tf, op); }
+        return py::make_tuple(jpvt, Tf); });
+    DEF("unmqr_geqp3", [](Side sd, Op op_, Matrix<T>& A, TriangularFactors<T> Tf, Matrix<T>& C, py::dict o) {
+        Options op = to_options(o); py::gil_scoped_release r; unmqr_geqp3(sd, op_, A, Tf, C, op); });
+    DEF("gelsy", [](Matrix<T>& A, Matrix<T>& BX, double rcond, py::dict o) {
+        Options op = to_options(o); py::gil_scoped_release r; return gelsy(A, BX, R(rcond), op); });
     DEF("gels_cholqr",[](Matrix<T>& A, Matrix<T>& Rm, Matrix<T>& BX, py::dict o) {
         Options op = to_options(o); py::gil_scoped_release r; gels_cholqr(A, Rm, BX, op); });
     DEF("gels_qr", [](Matrix<T>& A, Matrix<T>& BX, py::dict o) {

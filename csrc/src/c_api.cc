@@ -286,3 +286,27 @@ int slate_bdsbz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t
     return bisect_c<double>(true, range, vl, vu, il, iu, n, d, e, nfound, s, no, o);
 }
 }  // extern "C"
+
+// QR with column pivoting, real types
+#define SLATE_C_API_GEQP3(X, R)                                                                                \
+int slate_qr_factor_pivoted_##X(slate_Matrix_##X A, int64_t* jpvt, slate_TriangularFactors_##X T_, int no,    \
+                                slate_Options const* o) {                                                      \
+    return guarded([&]() { std::vector<int64_t> P;                                                             \
+        slate::geqp3(A->A, P, T_->T_, to_opts(no, o));                                                         \
+        slate_error_if_msg(!P.empty() && !jpvt, "qr_factor_pivoted: jpvt is null");                            \
+        std::copy(P.begin(), P.end(), jpvt);                                                                   \
+        return 0; }, -1); }                                                                                    \
+int slate_qr_pivoted_multiply_by_q_##X(slate_Side side, slate_Op op, slate_Matrix_##X A,                       \
+                                       slate_TriangularFactors_##X T_, slate_Matrix_##X C, int no,             \
+                                       slate_Options const* o) {                                               \
+    return guarded([&]() { slate::unmqr_geqp3(slate::Side(side), slate::Op(op), A->A, T_->T_, C->A,            \
+                                              to_opts(no, o)); return 0; }, -1); }                             \
+int slate_least_squares_solve_rank_##X(slate_Matrix_##X A, slate_Matrix_##X BX, R rcond, int64_t* rank,       \
+                                       int no, slate_Options const* o) {                                       \
+    return guarded([&]() { const int64_t r = slate::gelsy(A->A, BX->A, rcond, to_opts(no, o));                 \
+        if (rank) *rank = r;                                                                                   \
+        return 0; }, -1); }
+extern "C" {
+SLATE_C_API_GEQP3(r32, float)
+SLATE_C_API_GEQP3(r64, double)
+}  // extern "C"

@@ -702,22 +702,7 @@ void set_diag_rows(Matrix<T>& M, std::vector<T> const& dg, Target target) {
 
 namespace {
 
-/// Range guard shared by heev and svd (reference heev.cc:73-102, svd.cc:85-125):
-/// returns the factor alpha the matrix was scaled to (1 if untouched) and sets
-/// `bad` when ||A||_max is NaN or Inf.  A matrix with ||A||_max below
-/// sqrt(safe_min / eps) or above its reciprocal is scaled by alpha / ||A||_max,
-/// so the reductions neither underflow nor overflow; the caller rescales the
-/// eigen / singular values by ||A||_max / alpha afterwards.
-template <typename R>
-R range_alpha(R anorm, bool& bad) {
-    const R sml = std::numeric_limits<R>::min() / std::numeric_limits<R>::epsilon();
-    const R sqrt_sml = std::sqrt(sml), sqrt_big = R(1) / sqrt_sml;
-    bad = std::isnan(anorm) || std::isinf(anorm);
-    if (bad) return R(1);
-    if (anorm > R(0) && anorm < sqrt_sml) return sqrt_sml;
-    if (anorm > sqrt_big) return sqrt_big;
-    return R(1);
-}
+// The range guard of heev and svd is internal::range_alpha (internal.hh).
 
 /// Option::MethodEig / Option::MethodSVD ask for Sturm-count bisection ('b' as
 /// well as 'B', as 'q' is accepted for QR): values only.

@@ -1231,5 +1231,118 @@ void gebrd(int64_t m, int64_t n, R* A, int64_t lda, R* d, R* e, R* tauq, R* taup
 template void gebrd<float>(int64_t, int64_t, float*, int64_t, float*, float*, float*, float*, int64_t);
 template void gebrd<double>(int64_t, int64_t, double*, int64_t, double*, double*, double*, double*, int64_t);
 
+//------------------------------------------------------------------------------
+// QR with column pivoting (LAPACK geqp3 / laqps from the math), the host twin
+// of kernels/geqp3.hip: the same seven steps per column, and like it the panel
+// is not cut short when a downdated norm cannot be trusted: that column alone
+// has the pending update applied and its norm recomputed.
+template <typename R>
+int64_t geqp3(int64_t m, int64_t n, R* A, int64_t lda, int64_t* jpvt, R* tau, int64_t nb) {
+    for (int64_t c = 0; c < n; ++c) jpvt[c] = c;
+    const int64_t kmin = std::min(m, n);
+    if (kmin <= 0) return 0;
+    nb = std::max<int64_t>(1, nb);
+    const R tol3z = std::sqrt(std::numeric_limits<R>::epsilon() / 2);
+    std::vector<R> F(size_t(n) * nb), vn1(n), vn2(n), t(nb), w(n), v(m);
+    std::vector<char> flag(n, 0);
+    int64_t recomputes = 0;
+    for (int64_t c = 0; c < n; ++c) {
+        R ss = 0;
+        for (int64_t r = 0; r < m; ++r) ss += A[r + c * lda] * A[r + c * lda];
+        vn1[c] = vn2[c] = std::sqrt(ss);
+    }
+    for (int64_t j0 = 0; j0 < kmin; j0 += nb) {
+        const int64_t kb = std::min(nb, kmin - j0);
+        for (int64_t jj = 0; jj < kb; ++jj) {
+            const int64_t j = j0 + jj;
+            // 1, 2: pivot (the smallest index among equal maxima) and swap
+            int64_t p = j;
+            for (int64_t c = j + 1; c < n; ++c)
+                if (vn1[c] > vn1[p]) p = c;
+            if (p != j) {
+                for (int64_t r = 0; r < m; ++r) std::swap(A[r + j * lda], A[r + p * lda]);
+                for (int64_t k = 0; k < jj; ++k) std::swap(F[j + k * n], F[p + k * n]);
+                std::swap(vn1[j], vn1[p]);
+                std::swap(vn2[j], vn2[p]);
+                std::swap(jpvt[j], jpvt[p]);
+            }
+            // 3: A(j:m, j) -= V(j:m, :) F(j, 0:jj)^T
+            for (int64_t k = 0; k < jj; ++k) {
+                const R f = F[j + k * n];
+                const R* vk = A + (j0 + k) * lda;
+                for (int64_t r = j; r < m; ++r) A[r + j * lda] -= vk[r] * f;
+            }
+            // 4: larfg of A(j:m, j); R_jj stays on the diagonal, v holds the unit entry
+            R* a = A + j * lda;
+            R ss = 0, beta, scale;
+            for (int64_t r = j + 1; r < m; ++r) ss += a[r] * a[r];
+            larfg_tail<R>(a[j], ss, beta, tau[j], scale);
+            a[j] = beta;
+            v[j] = R(1);
+            for (int64_t r = j + 1; r < m; ++r) { a[r] *= scale; v[r] = a[r]; }
+            if (j + 1 >= n) break;
+            // 5: w = A(j:m, j+1:n)^T v, and the small dots V^T v
+            #pragma omp parallel for schedule(static)
+            for (int64_t c = j + 1; c < n; ++c) {
+                const R* ac = A + c * lda;
+                R s = 0;
+                for (int64_t r = j; r < m; ++r) s += ac[r] * v[r];
+                w[c] = s;
+            }
+            for (int64_t k = 0; k < jj; ++k) {
+                const R* vk = A + (j0 + k) * lda;
+                R s = 0;
+                for (int64_t r = j; r < m; ++r) s += vk[r] * v[r];
+                t[k] = s;
+            }
+            // 6: F(c, jj) = tau (w - F (V^T v)); row j: A(j, c) -= V(j, :) F(c, :)^T; norm downdate
+            for (int64_t c = j + 1; c < n; ++c) {
+                R s = w[c], rs = 0;
+                for (int64_t k = 0; k < jj; ++k) {
+                    const R fk = F[c + k * n];
+                    s -= fk * t[k];
+                    rs += fk * A[j + (j0 + k) * lda];
+                }
+                const R f = tau[j] * s;
+                F[c + jj * n] = f;
+                const R x = A[j + c * lda] - rs - f;
+                A[j + c * lda] = x;
+                if (vn1[c] != R(0)) {
+                    R y = std::abs(x) / vn1[c];
+                    y = std::max(R(0), (R(1) + y) * (R(1) - y));
+                    const R q = vn1[c] / vn2[c];
+                    if (y * q * q <= tol3z) flag[c] = 1;
+                    else vn1[c] *= std::sqrt(y);
+                }
+            }
+            for (int64_t r = j0; r <= j; ++r) F[r + jj * n] = R(0);
+            // 7: the flagged columns: the pending update applied to the column (its row of F
+            // cleared), so the new norm is that of the entries the factorization goes on with
+            for (int64_t c = j + 1; c < n; ++c) {
+                if (!flag[c]) continue;
+                R s = 0;
+                for (int64_t r = j + 1; r < m; ++r) {
+                    R x = A[r + c * lda];
+                    for (int64_t k = 0; k <= jj; ++k) x -= A[r + (j0 + k) * lda] * F[c + k * n];
+                    A[r + c * lda] = x;
+                    s += x * x;
+                }
+                for (int64_t k = 0; k <= jj; ++k) F[c + k * n] = R(0);
+                vn1[c] = vn2[c] = std::sqrt(s);
+                flag[c] = 0;
+                ++recomputes;
+            }
+        }
+        // trailing update: A22 -= V F^T
+        const int64_t k1 = j0 + kb;
+        if (k1 < n && k1 < m)
+            gemm(Op::NoTrans, Op::Trans, m - k1, n - k1, kb, R(-1), A + k1 + j0 * lda, lda, F.data() + k1, n, R(1),
+                 A + k1 + k1 * lda, lda);
+    }
+    return recomputes;
+}
+template int64_t geqp3<float>(int64_t, int64_t, float*, int64_t, int64_t*, float*, int64_t);
+template int64_t geqp3<double>(int64_t, int64_t, double*, int64_t, int64_t*, double*, int64_t);
+
 }  // namespace host
 }  // namespace slate

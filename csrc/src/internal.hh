@@ -9,8 +9,10 @@
 #include "slate_amd/runtime.hh"
 #include "slate_amd/trace.hh"
 
+#include <cmath>
 #include <cstdlib>
 #include <functional>
+#include <limits>
 #include <vector>
 
 namespace slate {
@@ -347,6 +349,43 @@ void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
 template <typename R>
 void unmbr_gebrd_local(lb::Ctx const& c, Vect vect, Side side, Op op, int64_t m, int64_t n, R const* A, int64_t lda,
                        R const* Tfac, int64_t mc, int64_t nc, R* C, int64_t ldc);
+
+/// geqp3's sibling of gebrd_check_operand: the same refusals, worded for the
+/// QR factorization with column pivoting
+template <typename T>
+void geqp3_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
+/// Panel width of the QR with column pivoting (geqp3.cc); T factors as gebrd's.
+constexpr int64_t kGeqp3Panel = 64;
+/// QR with column pivoting of the contiguous local m x n array A (c's memory):
+/// A P = Q R, R in the upper triangle / trapezoid, the min(m, n) reflectors
+/// below the diagonal with unit entries implied; tau (min(m, n)) and Tfac
+/// (kGeqp3Panel x n) in c's memory, jpvt (n, 0-based) on the host.  One host
+/// synchronisation, at the end.
+template <typename R>
+void geqp3_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std::vector<int64_t>& jpvt, R* tau,
+                 R* Tfac);
+/// C (mc x nc) := op(Q) C (Left) or C op(Q) (Right), Q (order m) of
+/// geqp3_local, one lb::larfb per panel; stream-ordered on the device.
+template <typename R>
+void unmqr_geqp3_local(lb::Ctx const& c, Side side, Op op, int64_t m, int64_t n, R const* A, int64_t lda,
+                       R const* Tfac, int64_t mc, int64_t nc, R* C, int64_t ldc);
+
+/// Range guard shared by heev, svd and gelsy (reference heev.cc:73-102,
+/// svd.cc:85-125): returns the factor alpha the matrix was scaled to (1 if
+/// untouched) and sets `bad` when ||A||_max is NaN or Inf.  A matrix with
+/// ||A||_max below sqrt(safe_min / eps) or above its reciprocal is scaled by
+/// alpha / ||A||_max, so the reductions neither underflow nor overflow; the
+/// caller rescales its results afterwards.
+template <typename R>
+R range_alpha(R anorm, bool& bad) {
+    const R sml = std::numeric_limits<R>::min() / std::numeric_limits<R>::epsilon();
+    const R sqrt_sml = std::sqrt(sml), sqrt_big = R(1) / sqrt_sml;
+    bad = std::isnan(anorm) || std::isinf(anorm);
+    if (bad) return R(1);
+    if (anorm > R(0) && anorm < sqrt_sml) return sqrt_sml;
+    if (anorm > sqrt_big) return sqrt_big;
+    return R(1);
+}
 
 /// Apply LU pivots to the rows of B (forward: P B; backward: P^T B).
 template <typename T>

@@ -1495,6 +1495,66 @@ Result r_gebrd(Case<T>& c, int variant) {   // 0 gebrd (A = Q B P^T), 1 unmbr_ge
 }
 
 template <typename T>
+Result r_geqp3(Case<T>& c, int variant) {   // 0 geqp3 (A P = Q R, Q^T Q = I), 1 gelsy (A^T (A X - B) = 0)
+    using R = R_<T>;
+    if (is_complex_v<T>) {
+        Result r; r.skipped = true; r.note = "real types (the QR with column pivoting)"; return r;
+    }
+    auto A = c.mat(c.m, c.n);
+    if (A.grid()->size() != 1) {
+        Result r; r.skipped = true; r.note = "a grid of one process (the QR with column pivoting)"; return r;
+    }
+    auto A0 = c.copy_of(A);
+    Result r;
+    const double m = double(c.m), n = double(c.n), k = double(std::min(c.m, c.n));
+    r.flops = cfac<T>() * (2.0 * m * n * k - (m + n) * k * k + 2.0 / 3 * k * k * k);
+    if (variant == 0) {
+        std::vector<int64_t> jpvt;
+        TriangularFactors<T> Tf;
+        r.time = c.timed([&] { geqp3(A, jpvt, Tf, c.opts); });
+        if (c.P.check) {
+            // Q R with R = triu(A) against A P, P as a matrix of zeros and ones
+            auto QR = c.zeros(c.m, c.n), Pm = c.zeros(c.n, c.n), AP = c.zeros(c.m, c.n);
+            BaseTrapezoidMatrix<T> Rt(Uplo::Upper, A, MatrixKind::Trapezoid), Qt(Uplo::Upper, QR, MatrixKind::Trapezoid);
+            copy<T, T>(Rt, Qt, c.opts);
+            unmqr_geqp3(Side::Left, Op::NoTrans, A, Tf, QR, c.opts);
+            set<T>(std::function<T(int64_t, int64_t)>([&](int64_t i, int64_t j) { return jpvt[j] == i ? T(1) : T(0); }),
+                   Pm, Options{{Option::Target, Target::Host}});
+            gemm(T(1), A0, Pm, T(0), AP, c.opts);
+            add(T(-1), AP, T(1), QR, c.opts);
+            const double e1 = c.nrm(QR) / (m * c.nrm(A0));
+            auto Q = c.zeros(c.m, c.m), G = c.zeros(c.m, c.m);
+            set(T(0), T(1), Q, c.opts);
+            set(T(0), T(1), G, c.opts);
+            unmqr_geqp3(Side::Left, Op::NoTrans, A, Tf, Q, c.opts);
+            gemm(T(1), conj_transpose(Q), Q, T(-1), G, c.opts);
+            r.error = std::max(e1, double(c.nrm(G)) / m);
+        }
+        return r;
+    }
+    auto BX = c.mat(std::max(c.m, c.n), c.P.nrhs);
+    auto B0 = c.copy_of(BX);
+    int64_t rank = 0;
+    const R rcond = std::numeric_limits<R>::epsilon() * R(std::max(c.m, c.n));
+    r.time = c.timed([&] { rank = gelsy(A, BX, rcond, c.opts); });
+    if (c.P.check) {
+        // the generated matrix has full rank: the checks of gels
+        Matrix<T> X = BX.slice(0, c.n - 1, 0, c.P.nrhs - 1);
+        auto Rr = c.copy_of(B0.slice(0, c.m - 1, 0, c.P.nrhs - 1));
+        gemm(T(-1), A0, X, T(1), Rr, c.opts);
+        if (c.m >= c.n) {
+            auto G = c.zeros(c.n, c.P.nrhs);
+            gemm(T(1), conj_transpose(A0), Rr, T(0), G, c.opts);        // A^T (b - A x) = 0
+            r.error = c.nrm(G) / (c.nrm(A0) * c.nrm(A0) * c.nrm(X) * n);
+        } else {
+            r.error = c.nrm(Rr) / (c.nrm(A0) * c.nrm(X) * n);
+        }
+        if (rank != std::min(c.m, c.n)) r.error = std::numeric_limits<double>::infinity();
+    }
+    return r;
+}
+
+template <typename T>
 Result r_hb2st(Case<T>& c, int variant) {   // 0 hb2st (Frobenius norm preserved), 1 unmtr_hb2st
     using R = R_<T>;
     auto A = herm_of(c, c.n);
@@ -2069,6 +2129,8 @@ std::map<std::string, Fn<T>> routines() {
         {"unmtr_hetrd", [](Case<T>& c) { return r_hetrd<T>(c, 1); }},
         {"gebrd", [](Case<T>& c) { return r_gebrd<T>(c, 0); }},
         {"unmbr_gebrd", [](Case<T>& c) { return r_gebrd<T>(c, 1); }},
+        {"geqp3", [](Case<T>& c) { return r_geqp3<T>(c, 0); }},
+        {"gelsy", [](Case<T>& c) { return r_geqp3<T>(c, 1); }},
         {"hb2st", [](Case<T>& c) { return r_hb2st<T>(c, 0); }},
         {"unmtr_hb2st", [](Case<T>& c) { return r_hb2st<T>(c, 1); }},
         {"ge2tb", r_ge2tb<T>},

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "gemv_t_block", "gemv_n_block", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "geqp3_stats", "gemv_t_block", "gemv_n_block", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -151,6 +151,18 @@ def gebrd_stats() -> dict:
     the kernels, recorded only when SLATE_GEBRD_PROFILE=1 is in the environment
     (zero otherwise)."""
     return _slate.gebrd_stats()
+
+
+def geqp3_stats() -> dict:
+    """Counters of the last QR with column pivoting of this process (geqp3, or
+    gelsy): `columns`, `panels`, `host_syncs` inside the factorization,
+    `norm_recomputes` (the columns whose norm was recomputed inside a panel,
+    counted on the device) and the launches of its kernels, launches_norms /
+    _pivot / _swap / _column / _larfg / _product / _finish / _recompute (zero
+    on the host target).  ms_pivot / ms_product / ms_panel / ms_gemm / ms_larft
+    are device milliseconds from events between the kernels, recorded only when
+    SLATE_GEQP3_PROFILE=1 is in the environment (zero otherwise)."""
+    return _slate.geqp3_stats()
 
 
 def _gemv_block(trans, A, x, row_offset, col_offset, repeat, use_lb):

@@ -365,6 +365,41 @@ def r_unmbr_gebrd(c):
     return t, err
 
 
+def r_geqp3(c):
+    _real_only(c)
+    a, A = c.mat(c.m, c.n)
+    t, (jpvt, T) = _timed(lambda: M.geqp3(A, target=c.target))
+    err = None
+    if c.a.check:
+        # ||A P - Q R|| / (||A|| n) and ||Q^T Q - I|| / m, Q from unmqr_geqp3 on the identity
+        k = min(c.m, c.n)
+        r = np.triu(core.to_numpy(A))[:k]
+        Q = core.from_numpy(np.eye(c.m, dtype=c.dt), nb=c.nb, target=c.target)
+        M.unmqr_geqp3(core.Side.Left, core.Op.NoTrans, A, T, Q, target=c.target)
+        q = core.to_numpy(Q)
+        d = np.abs(np.diag(r))
+        ok = sorted(jpvt.tolist()) == list(range(c.n)) and np.all(d[1:] <= (1 + 4 * np.sqrt(eps(c.dt))) * d[:-1])
+        err = max(np.linalg.norm(a[:, jpvt] - q[:, :k] @ r) / (np.linalg.norm(a) * c.n),
+                  np.linalg.norm(q.T @ q - np.eye(c.m)) / c.m) if ok else float("inf")
+    return t, err
+
+
+def r_gelsy(c):
+    _real_only(c)
+    a, A = c.mat(c.m, c.n)
+    b, B = c.mat(max(c.m, c.n), c.a.nrhs)
+    t, rank = _timed(lambda: M.gelsy(A, B, target=c.target))
+    err = None
+    if c.a.check:
+        # a random matrix has full rank: the normal-equations residual ||A^T (A x - b)|| / (||A||^2 ||x|| n)
+        x = core.to_numpy(B)[: c.n]
+        r = a.T @ (a @ x - b[: c.m])
+        err = np.linalg.norm(r) / (np.linalg.norm(a) ** 2 * np.linalg.norm(x) * c.n)
+        if rank != min(c.m, c.n):
+            err = float("inf")
+    return t, err
+
+
 def r_svd(c):
     a, A = c.mat(c.m, c.n)
     k = min(c.m, c.n)
@@ -508,6 +543,8 @@ ROUTINES = {
     "gebrd": (r_gebrd, lambda m, n, k: 4.0 * m * n * n - 4.0 / 3.0 * n ** 3),
     "unmbr_gebrd": (r_unmbr_gebrd, lambda m, n, k: 0.0),
     "svd": (r_svd, lambda m, n, k: 8.0 / 3.0 * n ** 3),
+    "geqp3": (r_geqp3, lambda m, n, k: F.geqrf_flops(m, n)),
+    "gelsy": (r_gelsy, lambda m, n, k: F.geqrf_flops(m, n)),
     "hesv": (r_hesv, lambda m, n, k: n ** 3 / 3.0),
     "gbsv": (r_gbsv, lambda m, n, k: 0.0),
     "genorm": (r_genorm, lambda m, n, k: 1.0 * m * n),
