@@ -10,6 +10,10 @@
 // on the whole local block instead of a batch of tile operations.
 #pragma once
 
+#include <string>
+#include <utility>
+#include <vector>
+
 #include "types.hh"
 #include "comm.hh"
 #include "device.hh"
@@ -77,6 +81,13 @@ private:
 GemmPrecision gemm_precision_option(Options const& opts);
 /// Launches of the split-operand bf16 kernel in this process so far.
 uint64_t lowprec_gemm_calls();
+/// Launches so far in this process of each native GEMM variant, by name: one
+/// entry per real / complex kernel instantiation (named after its template
+/// arguments: type, operand contiguity or ops, tile, waves, pipeline, store
+/// mask, interior-only or checked) and per dispatcher route (splitk,
+/// splitk_tri, pack_b_nt, pack_a_tn, gemv).  Variants whose launch site never
+/// ran are absent.
+std::vector<std::pair<std::string, uint64_t>> gemm_variant_counts();
 /// The raw kernel: C = alpha op(A) op(B) + beta C on device fp32 data, any
 /// shape; uplo General, or Lower / Upper for that triangle of a square C.
 void gemm_lowprec(Ctx const& c, GemmPrecision p, Uplo uplo, Op opA, Op opB, int64_t m, int64_t n, int64_t k,

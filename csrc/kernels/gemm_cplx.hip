@@ -219,9 +219,18 @@ void launch_cplx(int64_t m, int64_t n, int64_t k, cplx<R> alpha, const cplx<R>* 
                  int64_t ldb, cplx<R> beta, cplx<R>* C, int64_t ldc, hipStream_t stream) {
     const int mt = (int)((m + CBM - 1) / CBM), nt = (int)((n + CBN - 1) / CBN);
     const unsigned nblk = TRI ? (unsigned)(mt * (mt + 1) / 2) : (unsigned)(mt * nt);
-    // interior-only instantiation when every tile and K-tile is full
-    const bool full = (m % CBM == 0) && (n % CBN == 0) && (k % CBK == 0);
-    if (full && TRI == 0)
+    // interior-only instantiation when every tile and K-tile is full; it loads
+    // its first K-tile unconditionally, so k == 0 (C = beta C, operands without
+    // elements) takes the checked kernel, which then loads nothing
+    const bool full = (m % CBM == 0) && (n % CBN == 0) && (k % CBK == 0) && k > 0 && TRI == 0;
+    // one launch counter per instantiation, named after the template arguments
+    auto variant = [](const char* kind) {
+        return GemmVariantCounter("%c_%c%c_%dx%d_w%d_%c_%s", sizeof(R) == 8 ? 'z' : 'c', TA, TB, CBM, CBN, NTHR / 64,
+                                  TRI ? TRI : 'G', kind);
+    };
+    static GemmVariantCounter cnt[2] = {variant("checked"), variant("full")};
+    cnt[full].hit();
+    if (full)
         hipLaunchKernelGGL((gemm_cplx_mfma_kernel<R, TRI, TA, TB, false>), dim3(nblk), dim3(NTHR), 0, stream, m, n, k,
                            alpha, A, lda, B, ldb, beta, C, ldc);
     else

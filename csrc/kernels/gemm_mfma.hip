@@ -26,6 +26,8 @@
 #include "device_common.hh"
 #include "kernels.hh"
 
+#include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -42,6 +44,23 @@
 
 namespace slate_amd {
 namespace dev {
+
+// ---- launch counters of the GEMM variants (kernels.hh)
+namespace {
+std::atomic<GemmVariantCounter*> g_variant_head{nullptr};
+}
+GemmVariantCounter::GemmVariantCounter(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(name, sizeof(name), fmt, ap);
+    va_end(ap);
+    next = g_variant_head.load(std::memory_order_relaxed);
+    while (!g_variant_head.compare_exchange_weak(next, this, std::memory_order_release, std::memory_order_relaxed)) {}
+}
+void gemm_variant_counts(void (*fn)(const char*, uint64_t, void*), void* arg) {
+    for (GemmVariantCounter* c = g_variant_head.load(std::memory_order_acquire); c; c = c->next)
+        fn(c->name, c->count.load(std::memory_order_relaxed), arg);
+}
 
 template <typename T> struct Mfma;
 
@@ -458,10 +477,18 @@ static void launch_tile(int64_t m, int64_t n, int64_t k, T alpha,
     int64_t mt = (m + BM - 1) / BM, nt = (n + BN - 1) / BN;
     int64_t nblk = (TRI == 'L' || TRI == 'U') ? mt * (mt + 1) / 2 : mt * nt;
     dim3 grid((unsigned)nblk, (unsigned)batch);
+    // one launch counter per instantiation, named after the template arguments
+    auto variant = [](const char* kind) {
+        return GemmVariantCounter("%c_a%c_b%c_%dx%d_w%d_%s_%c_%s", sizeof(T) == 8 ? 'd' : 's', A_KC ? 'k' : 'm',
+                                  B_KC ? 'k' : 'n', BM, BN, NTHR / 64, ROT ? "rot" : "plain", TRI ? TRI : 'G', kind);
+    };
     // every tile interior (the common case for nb-multiple trailing updates):
     // a kernel without the bounds-checked path, whose registers then go to
     // the hot loop alone
-    if (aligned && m % BM == 0 && n % BN == 0 && k % BK == 0 && k > 0)
+    const bool ionly = aligned && m % BM == 0 && n % BN == 0 && k % BK == 0 && k > 0;
+    static GemmVariantCounter cnt[2] = {variant("checked"), variant("ionly")};
+    cnt[ionly].hit();
+    if (ionly)
         hipLaunchKernelGGL((gemm_mfma_kernel<T, BM, BN, BK, A_KC, B_KC, TRI, WTN, WTM, ROT, true>), grid, dim3(NTHR),
                            0, stream, m, n, k, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, aligned, sm);
     else

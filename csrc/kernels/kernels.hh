@@ -9,6 +9,7 @@
 #pragma once
 
 #include <hip/hip_runtime_api.h>
+#include <atomic>
 #include <cstdint>
 #include "dev_types.hh"
 #include "matgen_entry.hh"
@@ -408,6 +409,23 @@ template <typename T>
 void qr_tsqr_narrow(int64_t rows, int nn, T* A, int64_t lda, T* Tm, int64_t ldt, T* tau, T* work, hipStream_t s);
 
 // ---- GEMM (gemm_mfma.hip: real MFMA; gemm_cplx.hip: complex)
+/// Launch counter of one GEMM variant.  Each launch site keeps one as a
+/// function-local static, named after its own template arguments; the
+/// constructor (first launch only) formats the name and links the counter into
+/// a process-wide list, so a launch costs one relaxed increment.  Host code
+/// only.  Real kernels: <type>_a<m|k>_b<n|k>_<BM>x<BN>_w<waves>_<rot|plain>_
+/// <G|L|U|S>_<ionly|checked> (a/b: the contiguous dimension of the operand as
+/// stored); complex: <type>_<opA><opB>_64x64_w4_<G|L|U>_<full|checked>; the
+/// dispatcher's routes: splitk, splitk_tri, pack_b_nt, pack_a_tn, gemv.
+struct GemmVariantCounter {
+    char name[56];
+    std::atomic<uint64_t> count{0};
+    GemmVariantCounter* next = nullptr;
+    explicit GemmVariantCounter(const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+    void hit() { count.fetch_add(1, std::memory_order_relaxed); }
+};
+/// fn(name, launches, arg) for every variant whose launch site has run in this process
+void gemm_variant_counts(void (*fn)(const char* name, uint64_t count, void* arg), void* arg);
 template <typename T>
 void gemm_real(char transA, char transB, int64_t m, int64_t n, int64_t k,
                T alpha, const T* A, int64_t lda, int64_t sA,

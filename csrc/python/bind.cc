@@ -583,6 +583,11 @@ PYBIND11_MODULE(_slate, m) {
         slate_hip_call(hipStreamSynchronize(c.stream));
     });
     m.def("lowprec_gemm_calls", &lb::lowprec_gemm_calls);
+    m.def("gemm_variant_counts", []() {
+        py::dict r;
+        for (auto const& [name, count] : lb::gemm_variant_counts()) r[py::str(name)] = count;
+        return r;
+    });
     m.def("hetrd_stats", []() {
         const HetrdStats st = hetrd_stats();
         py::dict r;

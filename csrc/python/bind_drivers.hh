@@ -423,6 +423,13 @@ void bind_drivers(py::module_& m, std::string const& s) {
         lb::herk<T>(c, cup(up), cop(op), n, k, a, (T*)A, lda, b, (T*)C, ldc);
         dsync(c);
     });
+    DEF("lb_gemm_tri", [=](std::string up, std::string ta, std::string tb, int64_t n, int64_t k, T a, uintptr_t A,
+                           int64_t lda, uintptr_t B, int64_t ldb, T b, uintptr_t C, int64_t ldc) {
+        py::gil_scoped_release r;
+        auto c = dctx();
+        lb::gemm_tri<T>(c, cup(up), cop(ta), cop(tb), n, k, a, (T*)A, lda, (T*)B, ldb, b, (T*)C, ldc);
+        dsync(c);
+    });
     DEF("lb_trsm", [=](std::string sd, std::string up, std::string op, std::string dg, int64_t mm, int64_t n, T a,
                        uintptr_t A, int64_t lda, uintptr_t B, int64_t ldb) {
         py::gil_scoped_release r;

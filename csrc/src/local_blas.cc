@@ -176,6 +176,16 @@ GemmPrecision gemm_precision_option(Options const& opts) {
 
 uint64_t lowprec_gemm_calls() { return g_lowprec_calls.load(std::memory_order_relaxed); }
 
+std::vector<std::pair<std::string, uint64_t>> gemm_variant_counts() {
+    std::vector<std::pair<std::string, uint64_t>> out;
+    kd::gemm_variant_counts(
+        [](const char* name, uint64_t count, void* arg) {
+            static_cast<decltype(out)*>(arg)->emplace_back(name, count);
+        },
+        &out);
+    return out;
+}
+
 void gemm_lowprec(Ctx const& c, GemmPrecision p, Uplo uplo, Op opA, Op opB, int64_t m, int64_t n, int64_t k,
                   float alpha, float const* A, int64_t lda, float const* B, int64_t ldb, float beta, float* C,
                   int64_t ldc) {
@@ -190,6 +200,10 @@ void gemm_lowprec(Ctx const& c, GemmPrecision p, Uplo uplo, Op opA, Op opB, int6
 }
 
 namespace {
+// launch counters of the dispatcher's routes (gemm_variant_counts)
+kd::GemmVariantCounter g_route_splitk("splitk"), g_route_splitk_tri("splitk_tri"), g_route_pack_b_nt("pack_b_nt"),
+    g_route_pack_a_tn("pack_a_tn"), g_route_gemv("gemv");
+
 // SLATE_UPDATE_NT=0 keeps NN products in NN form (as internal::update_nt)
 inline bool nt_pack() {
     static const bool v = [] {
@@ -227,9 +241,11 @@ void dgemm(hipStream_t s, char uplo, Op opA, Op opB, int64_t m, int64_t n, int64
             // products, so the reduction stays a short streaming pass
             int64_t splits = std::min<int64_t>({ceildiv(k, 256), std::max<int64_t>(2, 512 / tiles), int64_t(64)});
             if (uplo == 'G') {
+                g_route_splitk.hit();
                 dgemm_splitk(s, ta, tb, m, n, k, splits, alpha, A, lda, B, ldb, beta, C, ldc);
                 return;
             }
+            g_route_splitk_tri.hit();
             // triangular store (herk / syrk of a tall panel, e.g. the Gram
             // matrix of a CholeskyQR pass, K = 32768 x 512: 4.5 ms on 16
             // workgroups): the full product split over K into scratch, then
@@ -250,8 +266,9 @@ void dgemm(hipStream_t s, char uplo, Op opA, Op opB, int64_t m, int64_t n, int64
         // reuse, so steady-state calls never reach hipMalloc)
         if (uplo == 'G' && ta == 'N' && tb == 'N' && sizeof(T) == 8 && nt_pack() && m >= 4096 &&
             n >= 1024 && k >= 256 && k <= 2048 && !(pack_a_on() && pack_a_form(m, n, k))) {
+            g_route_pack_b_nt.hit();
             const size_t bytes = size_t(n) * size_t(k) * sizeof(T);
-            T* Bt = static_cast<T*>(device::malloc_async(bytes, s));
+            T* Bt =static_cast<T*>(device::malloc_async(bytes, s));
             kd::gecopy<T, T>('G', 'T', n, k, B, ldb, Bt, n, s);
             kd::gemm_real<T>('N', 'T', m, n, k, alpha, A, lda, 0, Bt, n, 0, beta, C, ldc, 0, 1, s);
             device::free_async(Bt, s);
@@ -266,6 +283,7 @@ void dgemm(hipStream_t s, char uplo, Op opA, Op opB, int64_t m, int64_t n, int64
         // 8 GiB; later slices accumulate with beta = 1), so the scratch is
         // bounded independently of k and of the free HBM.
         if (pack_a_on() && uplo == 'G' && ta == 'N' && tb == 'N' && sizeof(T) == 8 && pack_a_form(m, n, k)) {
+            g_route_pack_a_tn.hit();
             const char* be = std::getenv("SLATE_GEMM_PACK_BYTES");
             const size_t budget = be ? size_t(std::atoll(be)) : (size_t(8) << 30);
             const int64_t kc = std::min<int64_t>(k, std::max<int64_t>(2048, int64_t(budget / (size_t(m) * sizeof(T))) / 256 * 256));
@@ -333,6 +351,7 @@ void gemm(Ctx const& c, Op opA, Op opB, int64_t m, int64_t n, int64_t k, T alpha
     if (n <= kSkinnyRhs && opB == Op::NoTrans) {
         // a few right-hand sides (residuals, refinement): memory-bound gemv
         // instead of 128-wide MFMA tiles with n live columns
+        g_route_gemv.hit();
         gemv(c, opA, m, k, n, alpha, A, lda, B, ldb, beta, C, ldc);
         return;
     }
@@ -387,6 +406,18 @@ void gemm_tri(Ctx const& c, Uplo uplo, Op opA, Op opB, int64_t n, int64_t k, T a
     dgemm(c.stream, upc(uplo), opA, opB, n, n, k, alpha, A, lda, B, ldb, beta, C, ldc, true);
 }
 
+namespace {
+// A Hermitian rank-k result has a real diagonal (BLAS zherk / zher2k, and
+// host::rankk / rank2k, set Im C(i,i) = 0); the triangular product leaves
+// beta Im C(i,i) plus rounding residue there.  One pass over the n diagonal
+// elements of the device result, complex types only.
+template <typename T>
+void real_diag(Ctx const& c, int64_t n, T* C, int64_t ldc) {
+    if constexpr (is_complex_v<T>)
+        kd::gen_diag('R', 0.0, n, n, dptr(C), ldc, n, 1, 0, 0, 0, n, 1, 0, 0, 0, c.stream);
+}
+}  // namespace
+
 template <typename T>
 void herk(Ctx const& c, Uplo uplo, Op op, int64_t n, int64_t k, real_type<T> alpha,
           T const* A, int64_t lda, real_type<T> beta, T* C, int64_t ldc) {
@@ -396,6 +427,7 @@ void herk(Ctx const& c, Uplo uplo, Op op, int64_t n, int64_t k, real_type<T> alp
     Op o1 = op == Op::NoTrans ? Op::NoTrans : Op::ConjTrans;
     Op o2 = op == Op::NoTrans ? Op::ConjTrans : Op::NoTrans;
     gemm_tri(c, uplo, o1, o2, n, k, T(alpha), A, lda, A, lda, T(beta), C, ldc);
+    real_diag(c, n, C, ldc);
 }
 
 template <typename T>
@@ -417,6 +449,7 @@ void her2k(Ctx const& c, Uplo uplo, Op op, int64_t n, int64_t k, T alpha, T cons
     Op o2 = op == Op::NoTrans ? Op::ConjTrans : Op::NoTrans;
     gemm_tri(c, uplo, o1, o2, n, k, alpha, A, lda, B, ldb, T(beta), C, ldc);
     gemm_tri(c, uplo, o1, o2, n, k, slate::conj(alpha), B, ldb, A, lda, T(1), C, ldc);
+    real_diag(c, n, C, ldc);
 }
 
 template <typename T>

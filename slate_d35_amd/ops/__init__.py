@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "geqp3_stats", "gemv_t_block", "gemv_n_block", "herk", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "geqp3_stats", "gemv_t_block", "gemv_n_block", "herk", "gemm_tri", "gemm_variant_counts", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -43,7 +43,12 @@ def _cm(t):
         # torch's own stream only: a device-wide synchronize would also wait
         # for work queued on the framework's queues (e.g. gemm_async)
         torch.cuda.current_stream(t.device).synchronize()
-    return t.data_ptr(), t.shape[1], t.shape[0], t.stride(0)
+    ptr = t.data_ptr()
+    if t.numel() == 0:
+        # torch reports a null pointer for an empty view; pass where the view
+        # lies in its allocation, as for any other operand
+        ptr = t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()
+    return ptr, t.shape[1], t.shape[0], t.stride(0)
 
 
 def gemm(opA: str, opB: str, alpha, A, B, beta, C):
@@ -215,6 +220,28 @@ def herk(uplo: str, op: str, alpha, A, beta, C):
     pc, n, _, ldc = _cm(C)
     k = na if op == "N" else ma
     fn(uplo, op, n, k, alpha, pa, lda, beta, pc, ldc)
+
+
+def gemm_tri(uplo: str, opA: str, opB: str, alpha, A, B, beta, C):
+    """The uplo ("L" / "U") triangle of the square C = alpha op(A) op(B) + beta C;
+    the other triangle is not touched.  Conventions of gemm."""
+    fn = getattr(_slate, f"lb_gemm_tri_{_suffix(C)}")
+    pa, ma, na, lda = _cm(A)
+    pb, mb, nb, ldb = _cm(B)
+    pc, n, _, ldc = _cm(C)
+    k = na if opA == "N" else ma
+    fn(uplo, opA, opB, n, k, alpha, pa, lda, pb, ldb, beta, pc, ldc)
+
+
+def gemm_variant_counts() -> dict:
+    """Launches so far in this process of each native GEMM variant, by name.
+    Real kernels: <s|d>_a<m|k>_b<n|k>_<BM>x<BN>_w<waves>_<rot|plain>_<G|L|U|S>_
+    <ionly|checked> (a / b: the contiguous dimension of the stored operand;
+    G general, L / U triangular, S staircase store); complex kernels:
+    <c|z>_<opA><opB>_64x64_w4_<G|L|U>_<full|checked>; dispatcher routes:
+    splitk, splitk_tri, pack_b_nt, pack_a_tn, gemv.  Names that never launched
+    may be absent."""
+    return _slate.gemm_variant_counts()
 
 
 def trsm(side: str, uplo: str, op: str, diag: str, alpha, A, B):
