@@ -9,6 +9,7 @@
 //                    per-workgroup sums of squares below it
 //   2 gebrd_larfg_u  beta, tauq from those sums (d_i = beta); u scaled in
 //                    place, unit entry stored, u copied to a contiguous vector
+//                    (larfg_vec.hip, as 5)
 //   3 gebrd_pass1    partials of A(i:m, i+1:n)^T u, and in the same grid the
 //                    partials of U^T u and X^T u
 //   4 gebrd_finish_y partials summed in a fixed order, y = tauq (A^T u -
@@ -23,16 +24,13 @@
 // kernel sums them again in the same order, so all workgroups see the same
 // bits and two runs give identical results.
 //
-// The two products: the block is cut into tiles of 64 rows x 16 columns.  A
-// lane owns one row of a tile, so a wave reads 64 consecutive elements of a
-// column: coalesced whatever the alignment of the block's base, which is only
-// element-aligned and moves every column.  A workgroup takes one block column
-// and 4 x tpw row tiles, its waves taking different tiles.  Pass 1 (A^T u)
-// keeps the 16 column partials in registers over the wave's tiles and reduces
-// them once through LDS; pass 2 (A v) writes each tile's row sums per block
+// The two products use the 64 x 16 tiles that reduce_tiles.hh describes; the
+// block's base is only element-aligned and moves every column.  Pass 1 (A^T u)
+// is gemv_t_tiles of that header, as are the small dots and their gather;
+// pass 2 (A v, gemv_n_tiles below) writes each tile's row sums per block
 // column.  Loads outside the block are masked: nothing outside it is read.
 #include "device_common.hh"
-#include "gemv_tiles.hh"
+#include "reduce_tiles.hh"
 #include "kernels.hh"
 
 #include <algorithm>
@@ -42,7 +40,7 @@ namespace dev {
 
 namespace {
 
-// GT, TR, TC, GR, the gb_* reductions, gb_larfg and gemv_t_tiles (A^T x): gemv_tiles.hh
+// GT, TR, TC, GR, KP, the gb_* reductions, gemv_t_tiles (A^T x), panel_dots and gather_pdots: reduce_tiles.hh
 
 // one workgroup of A x over the mr x nc block at A: block column J, chunk k.
 // rowpart[J * mr + r] = sum over the block column of A(r, j) x(j).  The wave's
@@ -130,7 +128,7 @@ template <typename R>
 __global__ __launch_bounds__(GT) void gebrd_column_kernel(int64_t m, int64_t i, int64_t j0, R* A, int64_t lda,
                                                           GebrdWork<R> wk) {
     __shared__ R sh[4];
-    __shared__ R Yi[64], Vi[64];
+    __shared__ R Yi[KP], Vi[KP];
     __shared__ R red[4][GR];
     const int c = int(i - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -158,23 +156,6 @@ __global__ __launch_bounds__(GT) void gebrd_column_kernel(int64_t m, int64_t i, 
     if (threadIdx.x == 0) wk.ssq[blockIdx.x] = ss;
 }
 
-// 2: rows r >= i.  larfg of A(i:m, i)
-template <typename R>
-__global__ __launch_bounds__(GT) void gebrd_larfg_u_kernel(int64_t m, int64_t i, R* A, int64_t lda, GebrdWork<R> wk,
-                                                           int nssq) {
-    __shared__ R sh[4];
-    const R ss = gb_partial_sum<R>(wk.ssq, nssq, sh);
-    R beta, tau, scale;
-    gb_larfg<R>(wk.scal[0], ss, beta, tau, scale);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { wk.d[i] = beta; wk.tauq[i] = tau; }
-    const int64_t r = i + int64_t(blockIdx.x) * GT + threadIdx.x;
-    if (r < m) {
-        const R val = r == i ? R(1) : A[r + i * lda] * scale;
-        A[r + i * lda] = val;
-        wk.u[r] = val;
-    }
-}
-
 // 3: partials of A(i:m, i+1:n)^T u, and (blockIdx.y >= nJ) the partials of
 // U^T u and X^T u over 256 rows each, one wave per column
 template <typename R>
@@ -188,32 +169,7 @@ __global__ __launch_bounds__(GT) void gebrd_pass1_kernel(int64_t m, int64_t n, i
     }
     const int64_t q = int64_t(blockIdx.y - nJ) * gridDim.x + blockIdx.x;
     if (q >= ndots) return;
-    const int c = int(i - j0);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t r0 = i + q * GT;
-    R ur[4];
-    #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int64_t r = r0 + lane + 64 * s;
-        ur[s] = r < m ? wk.u[r] : R(0);
-    }
-    for (int k = w; k < c; k += 4) {
-        R su = R(0), sx = R(0);
-        #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int64_t r = r0 + lane + 64 * s;
-            if (r < m) {
-                su += A[r + (j0 + k) * lda] * ur[s];
-                sx += wk.X[r + int64_t(k) * wk.ldx] * ur[s];
-            }
-        }
-        su = wave_sum(su);
-        sx = wave_sum(sx);
-        if (lane == 0) {
-            wk.pdots[q * 128 + k] = su;
-            wk.pdots[q * 128 + 64 + k] = sx;
-        }
-    }
+    panel_dots<R, true>(i + q * GT, m, wk.u, int(i - j0), A + j0 * lda, lda, wk.X, wk.ldx, wk.pdots + q * (2 * KP));
 }
 
 // 4: columns j > i, lane = column.  y_j finished and stored in Y(j, c), row i of A updated
@@ -221,16 +177,12 @@ template <typename R>
 __global__ __launch_bounds__(GT) void gebrd_finish_y_kernel(int64_t m, int64_t n, int64_t i, int64_t j0, R* A,
                                                             int64_t lda, GebrdWork<R> wk, int nk, int ndots) {
     __shared__ R sh[4];
-    __shared__ R t12[128];   // U^T u | X^T u
-    __shared__ R Ui[64], Xi[64];
+    __shared__ R t12[2 * KP];   // U^T u | X^T u
+    __shared__ R Ui[KP], Xi[KP];
     __shared__ R red[4][GR];
     const int c = int(i - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    if (threadIdx.x < 128 && lane < c) {
-        R s = R(0);
-        for (int q = 0; q < ndots; ++q) s += wk.pdots[int64_t(q) * 128 + threadIdx.x];
-        t12[threadIdx.x] = s;
-    }
+    gather_pdots<R>(wk.pdots, ndots, 2 * KP, c, c, t12);
     if (threadIdx.x >= 128 && threadIdx.x < 192 && lane < c) Ui[lane] = A[i + (j0 + lane) * lda];
     if (threadIdx.x >= 192 && lane < c) Xi[lane] = wk.X[i + int64_t(lane) * wk.ldx];
     __syncthreads();
@@ -244,7 +196,7 @@ __global__ __launch_bounds__(GT) void gebrd_finish_y_kernel(int64_t m, int64_t n
         #pragma unroll 4
         for (int k = g; k < c; k += 4) {
             const R yk = wk.Y[j + int64_t(k) * wk.ldy], vk = A[(j0 + k) + j * lda];
-            ys -= yk * t12[k] + vk * t12[64 + k];
+            ys -= yk * t12[k] + vk * t12[KP + k];
             rs += yk * Ui[k] + vk * Xi[k];
         }
     }
@@ -260,23 +212,6 @@ __global__ __launch_bounds__(GT) void gebrd_finish_y_kernel(int64_t m, int64_t n
     }
     const R ss = gb_block_sum<R>(g == 0 && inb && j > i + 1 ? a * a : R(0), sh);
     if (threadIdx.x == 0) wk.ssq2[blockIdx.x] = ss;
-}
-
-// 5: columns j > i.  larfg of A(i, i+1:n)
-template <typename R>
-__global__ __launch_bounds__(GT) void gebrd_larfg_v_kernel(int64_t n, int64_t i, R* A, int64_t lda, GebrdWork<R> wk,
-                                                           int nssq) {
-    __shared__ R sh[4];
-    const R ss = gb_partial_sum<R>(wk.ssq2, nssq, sh);
-    R beta, tau, scale;
-    gb_larfg<R>(wk.scal[1], ss, beta, tau, scale);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { wk.e[i] = beta; wk.taup[i] = tau; }
-    const int64_t j = i + 1 + int64_t(blockIdx.x) * GT + threadIdx.x;
-    if (j < n) {
-        const R val = j == i + 1 ? R(1) : A[i + j * lda] * scale;
-        A[i + j * lda] = val;
-        wk.v[j] = val;
-    }
 }
 
 // 6: partials of A(i+1:m, i+1:n) v, and (blockIdx.y >= nJ) the partials of
@@ -296,22 +231,7 @@ __global__ __launch_bounds__(GT) void gebrd_pass2_kernel(int64_t m, int64_t n, i
     const int c = int(i - j0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t c0 = i + 1 + q * GT;
-    R vr[4];
-    #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int64_t j = c0 + lane + 64 * s;
-        vr[s] = j < n ? wk.v[j] : R(0);
-    }
-    for (int k = w; k <= c; k += 4) {
-        R sy = R(0);
-        #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int64_t j = c0 + lane + 64 * s;
-            if (j < n) sy += wk.Y[j + int64_t(k) * wk.ldy] * vr[s];
-        }
-        sy = wave_sum(sy);
-        if (lane == 0) wk.pdots[q * 128 + k] = sy;
-    }
+    panel_dots<R, false>(c0, n, wk.v, c + 1, wk.Y, wk.ldy, nullptr, 0, wk.pdots + q * (2 * KP));
     // V v: lane = k, wave w takes columns c0 + 64 w .. + 63
     R sv = R(0);
     if (lane < c) {
@@ -319,22 +239,18 @@ __global__ __launch_bounds__(GT) void gebrd_pass2_kernel(int64_t m, int64_t n, i
         for (int64_t j = jb; j < je; ++j) sv += A[(j0 + lane) + j * lda] * wk.v[j];
     }
     sv = gb_waves_sum<R>(sv, red);
-    if (w == 0 && lane < c) wk.pdots[q * 128 + 64 + lane] = sv;
+    if (w == 0 && lane < c) wk.pdots[q * (2 * KP) + KP + lane] = sv;
 }
 
 // 7: rows r > i.  x_r finished and stored in X(r, c)
 template <typename R>
 __global__ __launch_bounds__(GT) void gebrd_finish_x_kernel(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A,
                                                             int64_t lda, GebrdWork<R> wk, int nJ, int ndots) {
-    __shared__ R t34[128];   // Y^T v (c + 1) | V v (c)
+    __shared__ R t34[2 * KP];   // Y^T v (c + 1) | V v (c)
     __shared__ R red[4][GR];
     const int c = int(i - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    if (threadIdx.x < 128 && lane < c + (threadIdx.x < 64 ? 1 : 0)) {
-        R s = R(0);
-        for (int q = 0; q < ndots; ++q) s += wk.pdots[int64_t(q) * 128 + threadIdx.x];
-        t34[threadIdx.x] = s;
-    }
+    gather_pdots<R>(wk.pdots, ndots, 2 * KP, c + 1, c, t34);
     __syncthreads();
     const int64_t mr = m - i - 1;
     const int64_t rl = int64_t(blockIdx.x) * GR + lane, r = i + 1 + rl;
@@ -346,7 +262,7 @@ __global__ __launch_bounds__(GT) void gebrd_finish_x_kernel(int64_t m, int64_t n
         #pragma unroll 4
         for (int k = g; k <= c; k += 4) {
             xs -= A[r + (j0 + k) * lda] * t34[k];
-            if (k < c) xs -= wk.X[r + int64_t(k) * wk.ldx] * t34[64 + k];
+            if (k < c) xs -= wk.X[r + int64_t(k) * wk.ldx] * t34[KP + k];
         }
     }
     xs = gb_waves_sum<R>(xs, red);
@@ -408,8 +324,8 @@ void gebrd_column(int64_t m, int64_t i, int64_t j0, R* A, int64_t lda, GebrdWork
 }
 template <typename R>
 void gebrd_larfg_u(int64_t m, int64_t i, R* A, int64_t lda, GebrdWork<R> const& wk, hipStream_t s) {
-    hipLaunchKernelGGL(gebrd_larfg_u_kernel<R>, dim3(gblocks_of(m - i)), dim3(GT), 0, s, m, i, A, lda, wk,
-                       int(grblocks_of(m - i)));
+    larfg_vec<R>(m - i, A + i + i * lda, 1, wk.scal, wk.ssq, int(grblocks_of(m - i)), wk.tauq + i, wk.d + i, wk.u + i,
+                 false, s);
 }
 template <typename R>
 void gebrd_pass1(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, GebrdWork<R> const& wk,
@@ -418,9 +334,8 @@ void gebrd_pass1(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_
     const int tpw = gemv_block_tpw(mr, nc);
     const int64_t nJ = (nc + TC - 1) / TC, nk = gemv_block_chunks(mr, tpw);
     const int64_t ndots = i > j0 ? gblocks_of(mr) : 0;
-    const int64_t extra = (ndots + nk - 1) / nk;
-    hipLaunchKernelGGL(gebrd_pass1_kernel<R>, dim3(unsigned(nk), unsigned(nJ + extra)), dim3(GT), 0, s, m, n, i, j0, A,
-                       lda, wk, tpw, int(nJ), int(ndots));
+    hipLaunchKernelGGL(gebrd_pass1_kernel<R>, product_grid(nk, nJ, ndots), dim3(GT), 0, s, m, n, i, j0, A, lda, wk, tpw,
+                       int(nJ), int(ndots));
 }
 template <typename R>
 void gebrd_finish_y(int64_t m, int64_t n, int64_t i, int64_t j0, R* A, int64_t lda, GebrdWork<R> const& wk,
@@ -433,8 +348,8 @@ void gebrd_finish_y(int64_t m, int64_t n, int64_t i, int64_t j0, R* A, int64_t l
 template <typename R>
 void gebrd_larfg_v(int64_t n, int64_t i, R* A, int64_t lda, GebrdWork<R> const& wk, hipStream_t s) {
     const int64_t nc = n - i - 1;
-    hipLaunchKernelGGL(gebrd_larfg_v_kernel<R>, dim3(gblocks_of(nc)), dim3(GT), 0, s, n, i, A, lda, wk,
-                       int(grblocks_of(nc)));
+    larfg_vec<R>(nc, A + i + (i + 1) * lda, lda, wk.scal + 1, wk.ssq2, int(grblocks_of(nc)), wk.taup + i, wk.e + i,
+                 wk.v + i + 1, false, s);
 }
 template <typename R>
 void gebrd_pass2(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, GebrdWork<R> const& wk,
@@ -444,9 +359,8 @@ void gebrd_pass2(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_
     const int64_t ndots = gblocks_of(nc);    // Y^T v has the new column of Y even when c = 0
     const int tpw = gemv_block_tpw(mr, nc);
     const int64_t nJ = (nc + TC - 1) / TC, nk = gemv_block_chunks(mr, tpw);
-    const int64_t extra = (ndots + nk - 1) / nk;
-    hipLaunchKernelGGL(gebrd_pass2_kernel<R>, dim3(unsigned(nk), unsigned(nJ + extra)), dim3(GT), 0, s, m, n, i, j0, A,
-                       lda, wk, tpw, int(nJ), int(ndots));
+    hipLaunchKernelGGL(gebrd_pass2_kernel<R>, product_grid(nk, nJ, ndots), dim3(GT), 0, s, m, n, i, j0, A, lda, wk, tpw,
+                       int(nJ), int(ndots));
 }
 template <typename R>
 void gebrd_finish_x(int64_t m, int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, GebrdWork<R> const& wk,

@@ -14,7 +14,7 @@
 //                     per-workgroup sums of squares below it
 //   4 geqp3_larfg     beta, tau from those sums (R_jj = beta stays in A); v
 //                     scaled in place and copied, with its unit entry, to a
-//                     contiguous vector
+//                     contiguous vector (larfg_vec.hip)
 //   5 geqp3_product   partials of A(j:m, j+1:n)^T v, and in the same grid the
 //                     partials of V(j:m, :)^T v
 //   6 geqp3_finish    partials summed in a fixed order, F(c, jj) = tau (A^T v -
@@ -29,10 +29,11 @@
 //                     and counts the recompute in the slot of its column
 // The last column of the matrix takes steps 3 and 4 only.  Every reduction has
 // two levels and a fixed order, so two runs give identical results.  The
-// product uses the 64 x 16 tiles of gemv_tiles.hh: one read of the trailing
-// block per column.  Loads outside the matrix are masked.
+// product uses the 64 x 16 tiles of reduce_tiles.hh, which also has the small
+// dots and their gather: one read of the trailing block per column.  Loads
+// outside the matrix are masked.
 #include "device_common.hh"
-#include "gemv_tiles.hh"
+#include "reduce_tiles.hh"
 #include "kernels.hh"
 
 #include <algorithm>
@@ -126,7 +127,7 @@ template <typename R>
 __global__ __launch_bounds__(GT) void geqp3_column_kernel(int64_t m, int64_t j, int64_t j0, R* A, int64_t lda,
                                                           Geqp3Work<R> wk) {
     __shared__ R sh[4];
-    __shared__ R Fj[64];
+    __shared__ R Fj[KP];
     __shared__ R red[4][GR];
     const int jj = int(j - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -150,28 +151,6 @@ __global__ __launch_bounds__(GT) void geqp3_column_kernel(int64_t m, int64_t j, 
     if (threadIdx.x == 0) wk.ssq[blockIdx.x] = ss;
 }
 
-// 4: rows r >= j.  larfg of A(j:m, j); R_jj = beta stays on the diagonal
-template <typename R>
-__global__ __launch_bounds__(GT) void geqp3_larfg_kernel(int64_t m, int64_t j, R* A, int64_t lda, Geqp3Work<R> wk,
-                                                         int nssq) {
-    __shared__ R sh[4];
-    const R ss = gb_partial_sum<R>(wk.ssq, nssq, sh);
-    R beta, tau, scale;
-    gb_larfg<R>(wk.scal[0], ss, beta, tau, scale);
-    if (blockIdx.x == 0 && threadIdx.x == 0) wk.tau[j] = tau;
-    const int64_t r = j + int64_t(blockIdx.x) * GT + threadIdx.x;
-    if (r < m) {
-        if (r == j) {
-            A[r + j * lda] = beta;
-            wk.v[r] = R(1);
-        } else {
-            const R val = A[r + j * lda] * scale;
-            A[r + j * lda] = val;
-            wk.v[r] = val;
-        }
-    }
-}
-
 // 5: partials of A(j:m, j+1:n)^T v, and (blockIdx.y >= nJ) the partials of
 // V(j:m, 0:jj)^T v over 256 rows each, one wave per column
 template <typename R>
@@ -185,41 +164,19 @@ __global__ __launch_bounds__(GT) void geqp3_product_kernel(int64_t m, int64_t n,
     }
     const int64_t q = int64_t(blockIdx.y - nJ) * gridDim.x + blockIdx.x;
     if (q >= ndots) return;
-    const int jj = int(j - j0);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t r0 = j + q * GT;
-    R vr[4];
-    #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int64_t r = r0 + lane + 64 * s;
-        vr[s] = r < m ? wk.v[r] : R(0);
-    }
-    for (int k = w; k < jj; k += 4) {
-        R sv = R(0);
-        #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int64_t r = r0 + lane + 64 * s;
-            if (r < m) sv += A[r + (j0 + k) * lda] * vr[s];
-        }
-        sv = wave_sum(sv);
-        if (lane == 0) wk.pdots[q * 64 + k] = sv;
-    }
+    panel_dots<R, false>(j + q * GT, m, wk.v, int(j - j0), A + j0 * lda, lda, nullptr, 0, wk.pdots + q * KP);
 }
 
 // 6: columns c > j, lane = column.  F(c, jj) finished, row j of A updated, vn1[c] downdated
 template <typename R>
 __global__ __launch_bounds__(GT) void geqp3_finish_kernel(int64_t m, int64_t n, int64_t j, int64_t j0, R* A,
                                                           int64_t lda, Geqp3Work<R> wk, int nk, int ndots) {
-    __shared__ R t[64];     // V^T v
-    __shared__ R Vj[64];    // row j of V
+    __shared__ R t[KP];     // V^T v
+    __shared__ R Vj[KP];    // row j of V
     __shared__ R red[4][GR];
     const int jj = int(j - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    if (g == 0 && lane < jj) {
-        R s = R(0);
-        for (int q = 0; q < ndots; ++q) s += wk.pdots[int64_t(q) * 64 + lane];
-        t[lane] = s;
-    }
+    gather_pdots<R>(wk.pdots, ndots, KP, jj, 0, t);
     if (g == 1 && lane < jj) Vj[lane] = A[j + (j0 + lane) * lda];
     // the rows of F that belong to the columns already factored are not read again
     if (blockIdx.x == 0 && g == 2 && lane <= jj) wk.F[(j0 + lane) + int64_t(jj) * wk.ldf] = R(0);
@@ -263,7 +220,7 @@ template <typename R>
 __global__ __launch_bounds__(GT) void geqp3_recompute_kernel(int64_t m, int64_t j, int64_t j0, R* A, int64_t lda,
                                                              Geqp3Work<R> wk) {
     __shared__ R sh[4];
-    __shared__ R Fc[64];
+    __shared__ R Fc[KP];
     const int64_t c = j + 1 + blockIdx.x;
     if (wk.flag[c] == 0) return;    // uniform over the workgroup
     const int jj = int(j - j0);
@@ -318,8 +275,8 @@ void geqp3_column(int64_t m, int64_t j, int64_t j0, R* A, int64_t lda, Geqp3Work
 }
 template <typename R>
 void geqp3_larfg(int64_t m, int64_t j, R* A, int64_t lda, Geqp3Work<R> const& wk, hipStream_t s) {
-    hipLaunchKernelGGL(geqp3_larfg_kernel<R>, dim3(gblocks_of(m - j)), dim3(GT), 0, s, m, j, A, lda, wk,
-                       int(grblocks_of(m - j)));
+    larfg_vec<R>(m - j, A + j + j * lda, 1, wk.scal, wk.ssq, int(grblocks_of(m - j)), wk.tau + j, nullptr, wk.v + j,
+                 true, s);
 }
 template <typename R>
 void geqp3_product(int64_t m, int64_t n, int64_t j, int64_t j0, const R* A, int64_t lda, Geqp3Work<R> const& wk,
@@ -329,9 +286,8 @@ void geqp3_product(int64_t m, int64_t n, int64_t j, int64_t j0, const R* A, int6
     const int tpw = gemv_block_tpw(mr, nc);
     const int64_t nJ = (nc + TC - 1) / TC, nk = gemv_block_chunks(mr, tpw);
     const int64_t ndots = j > j0 ? gblocks_of(mr) : 0;
-    const int64_t extra = (ndots + nk - 1) / nk;
-    hipLaunchKernelGGL(geqp3_product_kernel<R>, dim3(unsigned(nk), unsigned(nJ + extra)), dim3(GT), 0, s, m, n, j, j0,
-                       A, lda, wk, tpw, int(nJ), int(ndots));
+    hipLaunchKernelGGL(geqp3_product_kernel<R>, product_grid(nk, nJ, ndots), dim3(GT), 0, s, m, n, j, j0, A, lda, wk,
+                       tpw, int(nJ), int(ndots));
 }
 template <typename R>
 void geqp3_finish(int64_t m, int64_t n, int64_t j, int64_t j0, R* A, int64_t lda, Geqp3Work<R> const& wk,

@@ -8,14 +8,16 @@
 //                    w^T v), A(i:n, i) -= V W(i,:)^T + W V(i,:)^T, d_i, and
 //                    per-workgroup sums of squares of A(i+2:n, i)
 //   2 hetrd_larfg    beta, tau from those sums; v scaled in place, unit entry
-//                    stored, v copied to a contiguous vector
+//                    stored, v copied to a contiguous vector (larfg_vec.hip)
 //   3 hetrd_symv     partials of A(i+1:n, i+1:n) v from the lower triangle,
 //                    and in the same grid the partials of V^T v and W^T v
 //   4 hetrd_correct  partials summed in a fixed order, w -= V (W^T v) +
 //                    W (V^T v), per-workgroup partials of w^T v
 // Every reduction has two levels: partials go to a workspace, and each
 // workgroup of the next kernel sums them again in the same order, so all
-// workgroups see the same bits and two runs give identical results.
+// workgroups see the same bits and two runs give identical results.  The block
+// reductions, the small dots V^T v and W^T v and their gather are those of
+// gebrd.hip and geqp3.hip: reduce_tiles.hh.
 //
 // symv_lower: the block is cut into tiles of 64 rows x 16 columns.  A lane
 // owns one row of a tile (a wave reads 64 consecutive elements of a column:
@@ -24,9 +26,11 @@
 // and 16 column partials for y_J += A_IJ^T x_I.  A workgroup takes one block
 // column and 4 x tpw row tiles; its waves take different tiles, so the column
 // partials stay in registers over the tiles and are reduced once, and each
-// tile's row sums go out as they are.  The tile on the diagonal masks its
-// loads: the strict upper triangle is never read.
+// tile's row sums go out as they are (the reduction of the column partials is
+// gemv_t_tiles': reduce_tiles.hh).  The tile on the diagonal masks its loads:
+// the strict upper triangle is never read.
 #include "device_common.hh"
+#include "reduce_tiles.hh"
 #include "kernels.hh"
 
 #include <algorithm>
@@ -36,19 +40,7 @@ namespace dev {
 
 namespace {
 
-constexpr int HT = 256;    // threads of every kernel here
-constexpr int TR = 64;     // tile rows = lanes
-constexpr int TC = 16;     // tile columns
-
-// block sum, the same bits in every thread; all threads of the block call it
-template <typename R>
-__device__ inline R block_sum(R v, R* sh) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
+// GT, TR, TC, GR, KP, the gb_* reductions, gb_larfg, panel_dots and gather_pdots: reduce_tiles.hh
 
 // chunks of row tiles that block column J of an order-m block has
 __device__ inline int64_t symv_chunks_of(int64_t m, int tpw, int64_t J) {
@@ -93,45 +85,7 @@ __device__ inline void symv_tiles(int64_t m, const R* A, int64_t lda, const R* x
         }
         if (inb) rowpart[J * m + r] = racc;
     }
-    // column partials: lanes -> LDS, one thread per (wave, column) sums the 64 lanes in order
-    // into slot 64 of its row (not read by anyone before the next barrier), then the 4 waves
-    #pragma unroll
-    for (int c = 0; c < TC; ++c) cbuf[(w * TC + c) * 65 + lane] = cacc[c];
-    __syncthreads();
-    if (threadIdx.x < 4 * TC) {
-        const R* q = cbuf + threadIdx.x * 65;
-        R v = R(0);
-        for (int l = 0; l < 64; ++l) v += q[l];
-        cbuf[threadIdx.x * 65 + 64] = v;
-    }
-    __syncthreads();
-    if (int(threadIdx.x) < nc) {
-        const int c = threadIdx.x;
-        colpart[k * m + c0 + c] = (cbuf[(0 * TC + c) * 65 + 64] + cbuf[(1 * TC + c) * 65 + 64]) +
-                                  (cbuf[(2 * TC + c) * 65 + 64] + cbuf[(3 * TC + c) * 65 + 64]);
-    }
-}
-
-// rows per workgroup of the row kernels (symv_reduce, hetrd_column,
-// hetrd_correct): a lane owns a row and the 4 waves split the inner sums
-constexpr int HR = 64;
-
-// sum over the 4 waves of each lane's value, the same bits in all of them
-template <typename R>
-__device__ inline R waves_sum(R v, R (*red)[HR]) {
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    __syncthreads();
-    red[g][lane] = v;
-    __syncthreads();
-    return (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-}
-
-// sum of cnt workgroup partials, the same bits in every thread of every workgroup
-template <typename R>
-__device__ inline R partial_sum(const R* p, int cnt, R* sh) {
-    R s = R(0);
-    for (int q = threadIdx.x; q < cnt; q += HT) s += p[q];
-    return block_sum<R>(s, sh);
+    gb_colpart_reduce<R>(cacc, nc, colpart + k * m + c0, cbuf);
 }
 
 // wave g's share of y_i of the symv from its partials, in a fixed order
@@ -148,18 +102,18 @@ __device__ inline R symv_gather(int64_t m, int tpw, const R* rowpart, const R* c
 }
 
 template <typename R>
-__global__ __launch_bounds__(HT) void symv_lower_kernel(int64_t m, const R* A, int64_t lda, const R* x,
+__global__ __launch_bounds__(GT) void symv_lower_kernel(int64_t m, const R* A, int64_t lda, const R* x,
                                                            R* rowpart, R* colpart, int tpw) {
     __shared__ R cbuf[4 * TC * 65];
     symv_tiles<R>(m, A, lda, x, rowpart, colpart, tpw, blockIdx.x, blockIdx.y, cbuf);
 }
 
 template <typename R>
-__global__ __launch_bounds__(HT) void symv_reduce_kernel(int64_t m, const R* rowpart, const R* colpart, int tpw,
+__global__ __launch_bounds__(GT) void symv_reduce_kernel(int64_t m, const R* rowpart, const R* colpart, int tpw,
                                                          R* y) {
-    __shared__ R red[4][HR];
-    const int64_t i = int64_t(blockIdx.x) * HR + (threadIdx.x & 63);
-    const R v = waves_sum<R>(i < m ? symv_gather<R>(m, tpw, rowpart, colpart, i, threadIdx.x >> 6) : R(0), red);
+    __shared__ R red[4][GR];
+    const int64_t i = int64_t(blockIdx.x) * GR + (threadIdx.x & 63);
+    const R v = gb_waves_sum<R>(i < m ? symv_gather<R>(m, tpw, rowpart, colpart, i, threadIdx.x >> 6) : R(0), red);
     if (i < m && threadIdx.x < 64) y[i] = v;
 }
 
@@ -168,19 +122,19 @@ __global__ __launch_bounds__(HT) void symv_reduce_kernel(int64_t m, const R* row
 // the partials of wraw^T v.  update: column i of A updated, d_i, alpha and the
 // partial sums of squares below it.
 template <typename R>
-__global__ __launch_bounds__(HT) void hetrd_column_kernel(int64_t n, int64_t i, int64_t j0, int update, R* A,
+__global__ __launch_bounds__(GT) void hetrd_column_kernel(int64_t n, int64_t i, int64_t j0, int update, R* A,
                                                           int64_t lda, HetrdWork<R> wk, int npdot) {
     __shared__ R sh[4];
-    __shared__ R Wi[64], Vi[64];
-    __shared__ R red[4][HR];
+    __shared__ R Wi[KP], Vi[KP];
+    __shared__ R red[4][GR];
     const int c = int(i - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int64_t r = i + int64_t(blockIdx.x) * HR + lane;
+    const int64_t r = i + int64_t(blockIdx.x) * GR + lane;
     const bool inb = r < n;
     R wfin = R(0), tau_p = R(0), a2 = R(0);
     if (c > 0) {
         tau_p = wk.tau[i - 1];
-        a2 = R(0.5) * tau_p * tau_p * partial_sum<R>(wk.pdot, npdot, sh);
+        a2 = R(0.5) * tau_p * tau_p * gb_partial_sum<R>(wk.pdot, npdot, sh);
         if (inb) {
             wfin = tau_p * wk.wraw[r] - a2 * wk.v[r];
             if (g == 0) wk.W[r + int64_t(c - 1) * wk.ldw] = wfin;
@@ -202,7 +156,7 @@ __global__ __launch_bounds__(HT) void hetrd_column_kernel(int64_t n, int64_t i, 
             s += A[r + (j0 + k) * lda] * Wi[k] + wv * Vi[k];
         }
     }
-    s = waves_sum<R>(s, red);
+    s = gb_waves_sum<R>(s, red);
     R a = R(0);
     if (inb && g == 0) {
         a = A[r + i * lda] - s;
@@ -210,37 +164,14 @@ __global__ __launch_bounds__(HT) void hetrd_column_kernel(int64_t n, int64_t i, 
         if (r == i) wk.d[i] = a;
         if (r == i + 1) wk.scal[0] = a;
     }
-    const R ss = block_sum<R>(g == 0 && inb && r >= i + 2 ? a * a : R(0), sh);
+    const R ss = gb_block_sum<R>(g == 0 && inb && r >= i + 2 ? a * a : R(0), sh);
     if (threadIdx.x == 0) wk.ssq[blockIdx.x] = ss;
-}
-
-// 2: rows r >= i+1.  larfg of A(i+1:n, i).
-template <typename R>
-__global__ __launch_bounds__(HT) void hetrd_larfg_kernel(int64_t n, int64_t i, R* A, int64_t lda, HetrdWork<R> wk,
-                                                         int nssq) {
-    __shared__ R sh[4];
-    const R ss = partial_sum<R>(wk.ssq, nssq, sh);
-    const R alpha = wk.scal[0];
-    R beta = alpha, tau = R(0), scale = R(0);
-    if (ss != R(0)) {
-        const R nrm = sqrt(alpha * alpha + ss);
-        beta = alpha >= R(0) ? -nrm : nrm;
-        tau = (beta - alpha) / beta;
-        scale = R(1) / (alpha - beta);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { wk.e[i] = beta; wk.tau[i] = tau; }
-    const int64_t r = i + 1 + int64_t(blockIdx.x) * HT + threadIdx.x;
-    if (r < n) {
-        const R val = r == i + 1 ? R(1) : A[r + i * lda] * scale;
-        A[r + i * lda] = val;
-        wk.v[r] = val;
-    }
 }
 
 // 3: symv partials of the trailing block with v, and (blockIdx.y >= nJ) the
 // partials of V^T v and W^T v over 256 rows each, one wave per column
 template <typename R>
-__global__ __launch_bounds__(HT) void hetrd_symv_kernel(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda,
+__global__ __launch_bounds__(GT) void hetrd_symv_kernel(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda,
                                                         HetrdWork<R> wk, int tpw, int nJ, int ndots) {
     __shared__ R cbuf[4 * TC * 65];
     const int64_t o = i + 1, m = n - o;
@@ -250,72 +181,40 @@ __global__ __launch_bounds__(HT) void hetrd_symv_kernel(int64_t n, int64_t i, in
     }
     const int64_t q = int64_t(blockIdx.y - nJ) * gridDim.x + blockIdx.x;
     if (q >= ndots) return;
-    const int c = int(i - j0);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t r0 = o + q * HT;
-    R vr[4];
-    #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int64_t r = r0 + lane + 64 * s;
-        vr[s] = r < n ? wk.v[r] : R(0);
-    }
-    for (int k = w; k < c; k += 4) {
-        R sv = R(0), sw = R(0);
-        #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int64_t r = r0 + lane + 64 * s;
-            if (r < n) {
-                sv += A[r + (j0 + k) * lda] * vr[s];
-                sw += wk.W[r + int64_t(k) * wk.ldw] * vr[s];
-            }
-        }
-        sv = wave_sum(sv);
-        sw = wave_sum(sw);
-        if (lane == 0) {
-            wk.pvw[q * 128 + k] = sv;
-            wk.pvw[q * 128 + 64 + k] = sw;
-        }
-    }
+    panel_dots<R, true>(o + q * GT, n, wk.v, int(i - j0), A + j0 * lda, lda, wk.W, wk.ldw, wk.pvw + q * (2 * KP));
 }
 
 // 4: rows r >= i+1.  wraw = A v - V (W^T v) - W (V^T v), partials of wraw^T v
 template <typename R>
-__global__ __launch_bounds__(HT) void hetrd_correct_kernel(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda,
+__global__ __launch_bounds__(GT) void hetrd_correct_kernel(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda,
                                                            HetrdWork<R> wk, int tpw, int ndots) {
     __shared__ R sh[4];
-    __shared__ R tvw[128];   // V^T v | W^T v
-    __shared__ R red[4][HR];
+    __shared__ R tvw[2 * KP];   // V^T v | W^T v
+    __shared__ R red[4][GR];
     const int c = int(i - j0);
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-    if (threadIdx.x < 128 && lane < c) {
-        R s = R(0);
-        for (int q = 0; q < ndots; ++q) s += wk.pvw[int64_t(q) * 128 + threadIdx.x];
-        tvw[threadIdx.x] = s;
-    }
+    gather_pdots<R>(wk.pvw, ndots, 2 * KP, c, c, tvw);
     __syncthreads();
     const int64_t o = i + 1, m = n - o;
-    const int64_t r = o + int64_t(blockIdx.x) * HR + lane;
+    const int64_t r = o + int64_t(blockIdx.x) * GR + lane;
     R part = R(0);
     if (r < n) {
         part = symv_gather<R>(m, tpw, wk.rowpart, wk.colpart, r - o, g);
         R s = R(0);
         #pragma unroll 4
         for (int k = g; k < c; k += 4)
-            s += A[r + (j0 + k) * lda] * tvw[64 + k] + wk.W[r + int64_t(k) * wk.ldw] * tvw[k];
+            s += A[r + (j0 + k) * lda] * tvw[KP + k] + wk.W[r + int64_t(k) * wk.ldw] * tvw[k];
         part -= s;
     }
-    const R wr = waves_sum<R>(part, red);
+    const R wr = gb_waves_sum<R>(part, red);
     R p = R(0);
     if (r < n && g == 0) {
         wk.wraw[r] = wr;
         p = wr * wk.v[r];
     }
-    p = block_sum<R>(p, sh);
+    p = gb_block_sum<R>(p, sh);
     if (threadIdx.x == 0) wk.pdot[blockIdx.x] = p;
 }
-
-inline unsigned blocks_of(int64_t rows) { return unsigned((rows + HT - 1) / HT); }
-inline unsigned rblocks_of(int64_t rows) { return unsigned((rows + HR - 1) / HR); }
 
 }  // namespace
 
@@ -339,38 +238,37 @@ void symv_lower(int64_t m, const R* A, int64_t lda, const R* x, R* y, R* work, h
     const int64_t nJ = (m + TC - 1) / TC, nk = symv_lower_chunks(m, tpw);
     R* rowpart = work;
     R* colpart = work + nJ * m;
-    hipLaunchKernelGGL(symv_lower_kernel<R>, dim3(unsigned(nk), unsigned(nJ)), dim3(HT), 0, s, m, A, lda, x, rowpart,
+    hipLaunchKernelGGL(symv_lower_kernel<R>, dim3(unsigned(nk), unsigned(nJ)), dim3(GT), 0, s, m, A, lda, x, rowpart,
                        colpart, tpw);
-    hipLaunchKernelGGL(symv_reduce_kernel<R>, dim3(rblocks_of(m)), dim3(HT), 0, s, m, rowpart, colpart, tpw, y);
+    hipLaunchKernelGGL(symv_reduce_kernel<R>, dim3(grblocks_of(m)), dim3(GT), 0, s, m, rowpart, colpart, tpw, y);
 }
 
 template <typename R>
 void hetrd_column(int64_t n, int64_t i, int64_t j0, bool update, R* A, int64_t lda, HetrdWork<R> const& wk,
                   hipStream_t s) {
     if (i >= n) return;
-    const unsigned g = rblocks_of(n - i);
-    hipLaunchKernelGGL(hetrd_column_kernel<R>, dim3(g), dim3(HT), 0, s, n, i, j0, update ? 1 : 0, A, lda, wk, int(g));
+    const unsigned g = grblocks_of(n - i);
+    hipLaunchKernelGGL(hetrd_column_kernel<R>, dim3(g), dim3(GT), 0, s, n, i, j0, update ? 1 : 0, A, lda, wk, int(g));
 }
 template <typename R>
 void hetrd_larfg(int64_t n, int64_t i, R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s) {
-    hipLaunchKernelGGL(hetrd_larfg_kernel<R>, dim3(blocks_of(n - i - 1)), dim3(HT), 0, s, n, i, A, lda, wk,
-                       int(rblocks_of(n - i)));
+    larfg_vec<R>(n - i - 1, A + (i + 1) + i * lda, 1, wk.scal, wk.ssq, int(grblocks_of(n - i)), wk.tau + i, wk.e + i,
+                 wk.v + i + 1, false, s);
 }
 template <typename R>
 void hetrd_symv(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s) {
     const int64_t m = n - i - 1;
     const int tpw = symv_lower_tpw(m);
     const int64_t nJ = (m + TC - 1) / TC, nk = symv_lower_chunks(m, tpw);
-    const int64_t ndots = i > j0 ? blocks_of(m) : 0;
-    const int64_t extra = (ndots + nk - 1) / nk;
-    hipLaunchKernelGGL(hetrd_symv_kernel<R>, dim3(unsigned(nk), unsigned(nJ + extra)), dim3(HT), 0, s, n, i, j0, A, lda,
-                       wk, tpw, int(nJ), int(ndots));
+    const int64_t ndots = i > j0 ? gblocks_of(m) : 0;
+    hipLaunchKernelGGL(hetrd_symv_kernel<R>, product_grid(nk, nJ, ndots), dim3(GT), 0, s, n, i, j0, A, lda, wk, tpw,
+                       int(nJ), int(ndots));
 }
 template <typename R>
 void hetrd_correct(int64_t n, int64_t i, int64_t j0, const R* A, int64_t lda, HetrdWork<R> const& wk, hipStream_t s) {
     const int64_t m = n - i - 1;
-    hipLaunchKernelGGL(hetrd_correct_kernel<R>, dim3(rblocks_of(m)), dim3(HT), 0, s, n, i, j0, A, lda, wk,
-                       symv_lower_tpw(m), i > j0 ? int(blocks_of(m)) : 0);
+    hipLaunchKernelGGL(hetrd_correct_kernel<R>, dim3(grblocks_of(m)), dim3(GT), 0, s, n, i, j0, A, lda, wk,
+                       symv_lower_tpw(m), i > j0 ? int(gblocks_of(m)) : 0);
 }
 
 #define SLATE_INST_HETRD(R)                                                                                  \

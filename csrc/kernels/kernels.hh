@@ -212,6 +212,18 @@ struct StebzRefine {
 template <typename R>
 void stebz_refine(StebzRefine<R> const& a, int64_t max_values, hipStream_t s);
 
+// ---- shared by the one-stage reductions (reduce_tiles.hh, larfg_vec.hip), float and double
+/// columns of a panel of hetrd, gebrd and geqp3: the kernels size their LDS
+/// rows and the slots of the small-dot partials by it
+constexpr int kReducePanel = 64;
+/// larfg of the len entries x[0], x[incx], ..: alpha = *alpha (the head),
+/// the sum of squares of the tail = the sum of the nssq partials at ssq.
+/// *tau_out = tau, *beta_out = beta unless null; the tail is scaled in place,
+/// x[0] becomes beta (keep_beta) or 1, and v (contiguous) gets 1 and the tail.
+template <typename R>
+void larfg_vec(int64_t len, R* x, int64_t incx, const R* alpha, const R* ssq, int nssq, R* tau_out, R* beta_out, R* v,
+               bool keep_beta, hipStream_t s);
+
 // ---- one-stage tridiagonal reduction (hetrd.hip), float and double
 /// y = A x for the order-m symmetric block of which only the lower triangle is
 /// read (the strict upper triangle is never loaded).  No atomics: partials in

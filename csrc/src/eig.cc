@@ -16,6 +16,7 @@
 // stage-1 back-transform runs distributed (unmqr / unmlq on Z, U, VT).  No
 // rank holds an n x n array on the host.
 #include "internal.hh"
+#include "reduce_common.hh"
 #include "spread.hh"
 #include "eig_sinks.hh"
 #include "slate_amd/eig_host.hh"

@@ -11,26 +11,15 @@
 // larft recurrence (for P on the transposed row block), the back-transforms one
 // lb::larfb per panel.  The host target runs host::gebrd (eig_host.cc), the
 // same algorithm in plain loops.
-#include "internal.hh"
-#include "slate_amd/eig_host.hh"
-#include "slate_amd/host_blas.hh"
-#include "../kernels/kernels.hh"
-
-#include <algorithm>
-#include <cstdlib>
-#include <mutex>
+#include "reduce_common.hh"
 
 namespace slate {
 
 namespace {
-std::mutex g_stats_mu;
-GebrdStats g_stats;   // of the last reduction in this process
+internal::LastStats<GebrdStats> g_stats;   // of the last reduction in this process
 }  // namespace
 
-GebrdStats gebrd_stats() {
-    std::lock_guard<std::mutex> lk(g_stats_mu);
-    return g_stats;
-}
+GebrdStats gebrd_stats() { return g_stats.get(); }
 
 namespace lb {
 
@@ -56,41 +45,8 @@ template void gemv_block<double>(Ctx const&, Op, int64_t, int64_t, double const*
 namespace internal {
 
 namespace {
-
-/// SLATE_GEBRD_PROFILE=1: events between the kernels of the device reduction,
-/// summed per kind into GebrdStats::ms_* after the final synchronisation (no
-/// extra synchronisation; the records cost a few microseconds each, so the
-/// profile is for the split, not for the total).
-struct GebrdProfile {
-    enum Kind { Start = -1, Panel = 0, Pass1 = 1, Pass2 = 2, Gemm = 3, Larft = 4 };
-    bool on = false;
-    hipStream_t s = nullptr;
-    std::vector<std::pair<hipEvent_t, int>> ev;
-    GebrdProfile(hipStream_t st) : s(st) {
-        const char* e = std::getenv("SLATE_GEBRD_PROFILE");
-        on = e && std::atoi(e) != 0;
-    }
-    void mark(int kind) {   // the interval that ends here is of this kind
-        if (!on) return;
-        hipEvent_t x;
-        slate_hip_call(hipEventCreate(&x));
-        slate_hip_call(hipEventRecord(x, s));
-        ev.push_back({x, kind});
-    }
-    void finish(GebrdStats& st) {   // after the stream was synchronised
-        double ms[5] = {0, 0, 0, 0, 0};
-        for (size_t k = 1; k < ev.size(); ++k) {
-            float t = 0;
-            slate_hip_call(hipEventElapsedTime(&t, ev[k - 1].first, ev[k].first));
-            if (ev[k].second >= 0) ms[ev[k].second] += t;
-        }
-        for (auto& x : ev) slate_hip_call(hipEventDestroy(x.first));
-        ev.clear();
-        st.ms_panel = ms[Panel]; st.ms_pass1 = ms[Pass1]; st.ms_pass2 = ms[Pass2]; st.ms_gemm = ms[Gemm];
-        st.ms_larft = ms[Larft];
-    }
-};
-
+/// SLATE_GEBRD_PROFILE=1 (StageProfile): the kinds of GebrdStats::ms_*
+enum GebrdKind { Panel = 0, Pass1 = 1, Pass2 = 2, Gemm = 3, Larft = 4, Kinds = 5 };
 }  // namespace
 
 template <typename R>
@@ -103,25 +59,27 @@ void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
     e.assign(std::max<int64_t>(n - 1, 0), R(0));
     if (n == 0) return;
     GebrdStats st;
+    // T factors: every panel's reflectors are final (later panels touch A(k1:, k1:) only); P's from
+    // the transposed row block, explicit in Vx
+    Work<R> Vx(c.dev() ? Target::Devices : Target::Host, size_t(m) * nb);
+    auto t_factors = [&]() {
+        for (int64_t j0 = 0; j0 < n; j0 += nb) {
+            panel_T_factors<R>(c, m - j0, std::min(nb, n - j0), A + j0 + j0 * lda, lda, tauq + j0, TQ + j0 * nb, nb,
+                               Vx.data());
+            const int64_t kp = std::min(nb, n - 1 - j0), nv = n - j0 - 1;
+            if (kp <= 0) continue;
+            form_vt<R>(c, nv, kp, A + j0 + (j0 + 1) * lda, lda, Vx.data(), nv);
+            panel_T_factors<R>(c, nv, kp, nullptr, 0, taup + j0, TP + j0 * nb, nb, Vx.data());
+        }
+    };
     if (!c.dev()) {
         std::vector<R> eh(n, R(0));
         host::gebrd<R>(m, n, A, lda, d.data(), eh.data(), tauq, taup, nb);
         std::copy(eh.begin(), eh.begin() + (n - 1), e.begin());
-        std::vector<R> Vt(size_t(n) * nb);
-        for (int64_t j0 = 0; j0 < n; j0 += nb) {
-            const int64_t kb = std::min(nb, n - j0);
-            host::larft<R>(m - j0, kb, A + j0 + j0 * lda, lda, tauq + j0, TQ + j0 * nb, nb);
-            const int64_t kp = std::min(nb, n - 1 - j0), nv = n - j0 - 1;
-            if (kp > 0) {
-                for (int64_t k = 0; k < kp; ++k)
-                    for (int64_t j = 0; j < nv; ++j) Vt[j + k * nv] = A[(j0 + k) + (j0 + 1 + j) * lda];
-                host::larft<R>(nv, kp, Vt.data(), nv, taup + j0, TP + j0 * nb, nb);
-            }
-            ++st.panels;
-            st.columns += kb;
-        }
-        std::lock_guard<std::mutex> lk(g_stats_mu);
-        g_stats = st;
+        t_factors();
+        st.panels = (n + nb - 1) / nb;
+        st.columns = n;
+        g_stats.set(st);
         return;
     }
     hipStream_t s = c.stream;
@@ -146,8 +104,8 @@ void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
     wk.taup = taup;
     wk.colpart = part.data();
     wk.rowpart = part.data() + ncolpart;
-    GebrdProfile prof(s);
-    prof.mark(GebrdProfile::Start);
+    StageProfile prof("SLATE_GEBRD_PROFILE", Kinds, s);
+    prof.mark(StageProfile::Start);
     for (int64_t j0 = 0; j0 < n; j0 += nb) {
         const int64_t kb = std::min(nb, n - j0), k1 = j0 + kb;
         {
@@ -157,15 +115,15 @@ void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
                 kd::gebrd_larfg_u<R>(m, i, A, lda, wk, s);
                 ++st.launches_column;
                 ++st.launches_larfg_u;
-                if (i == n - 1) { prof.mark(GebrdProfile::Panel); break; }
-                prof.mark(GebrdProfile::Panel);
+                if (i == n - 1) { prof.mark(Panel); break; }
+                prof.mark(Panel);
                 kd::gebrd_pass1<R>(m, n, i, j0, A, lda, wk, s);
-                prof.mark(GebrdProfile::Pass1);
+                prof.mark(Pass1);
                 kd::gebrd_finish_y<R>(m, n, i, j0, A, lda, wk, s);
                 kd::gebrd_larfg_v<R>(n, i, A, lda, wk, s);
-                prof.mark(GebrdProfile::Panel);
+                prof.mark(Panel);
                 kd::gebrd_pass2<R>(m, n, i, j0, A, lda, wk, s);
-                prof.mark(GebrdProfile::Pass2);
+                prof.mark(Pass2);
                 kd::gebrd_finish_x<R>(m, n, i, j0, A, lda, wk, s);
                 ++st.launches_pass1;
                 ++st.launches_finish_y;
@@ -173,7 +131,7 @@ void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
                 ++st.launches_pass2;
                 ++st.launches_finish_x;
             }
-            prof.mark(GebrdProfile::Panel);
+            prof.mark(Panel);
         }
         st.columns += kb;
         ++st.panels;
@@ -183,74 +141,43 @@ void gebrd_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
                      R(1), A + k1 + k1 * lda, lda);
             lb::gemm(c, Op::NoTrans, Op::NoTrans, m - k1, n - k1, kb, R(-1), wk.X + k1, wk.ldx, A + j0 + k1 * lda, lda,
                      R(1), A + k1 + k1 * lda, lda);
-            prof.mark(GebrdProfile::Gemm);
+            prof.mark(Gemm);
         }
     }
     {
-        // T factors: every panel's reflectors are final (later panels touch A(k1:, k1:) only)
         trace::Block tt("gebrd_larft");
-        Work<R> Vx(Target::Devices, size_t(m) * nb);
-        for (int64_t j0 = 0; j0 < n; j0 += nb) {
-            const int64_t kb = std::min(nb, n - j0), mv = m - j0;
-            R* Tq = TQ + j0 * nb;
-            lb::form_v(c, mv, kb, A + j0 + j0 * lda, lda, Vx.data(), mv);
-            lb::gemm_splitk(c, Op::Trans, Op::NoTrans, kb, kb, mv, std::max<int64_t>(1, std::min<int64_t>(32, mv / 512)),
-                            R(1), Vx.data(), mv, Vx.data(), mv, R(0), Tq, nb);
-            kd::larft_small<R>(int(kb), tauq + j0, Tq, nb, s);
-            const int64_t kp = std::min(nb, n - 1 - j0), nv = n - j0 - 1;
-            if (kp <= 0) continue;
-            R* Tp = TP + j0 * nb;
-            kd::gebrd_form_vt<R>(nv, int(kp), A + j0 + (j0 + 1) * lda, lda, Vx.data(), nv, s);
-            lb::gemm_splitk(c, Op::Trans, Op::NoTrans, kp, kp, nv, std::max<int64_t>(1, std::min<int64_t>(32, nv / 512)),
-                            R(1), Vx.data(), nv, Vx.data(), nv, R(0), Tp, nb);
-            kd::larft_small<R>(int(kp), taup + j0, Tp, nb, s);
-        }
-        prof.mark(GebrdProfile::Larft);
+        t_factors();
+        prof.mark(Larft);
     }
     device::memcpy_async(d.data(), wk.d, size_t(n) * sizeof(R), s);
     if (n > 1) device::memcpy_async(e.data(), wk.e, size_t(n - 1) * sizeof(R), s);
     slate_hip_call(hipStreamSynchronize(s));
     st.host_syncs = 1;
-    prof.finish(st);
-    std::lock_guard<std::mutex> lk(g_stats_mu);
-    g_stats = st;
+    const std::vector<double> ms = prof.finish();
+    st.ms_panel = ms[Panel]; st.ms_pass1 = ms[Pass1]; st.ms_pass2 = ms[Pass2]; st.ms_gemm = ms[Gemm];
+    st.ms_larft = ms[Larft];
+    g_stats.set(st);
 }
 
 template <typename R>
 void unmbr_gebrd_local(lb::Ctx const& c, Vect vect, Side side, Op op, int64_t m, int64_t n, R const* A, int64_t lda,
                        R const* Tfac, int64_t mc, int64_t nc, R* C, int64_t ldc) {
-    namespace kd = slate_amd::dev;
     const int64_t nb = kGebrdPanel;
     const bool q = vect == Vect::Q;
     const int64_t order = q ? m : n, nref = q ? n : n - 1;   // reflectors
     slate_error_if_msg((side == Side::Left ? mc : nc) != order,
                        q ? "unmbr_gebrd: C does not match Q" : "unmbr_gebrd: C does not match P");
-    if (nref <= 0 || mc <= 0 || nc <= 0) return;
-    const int64_t np = (nref + nb - 1) / nb;
-    // F = F_0 F_1 .. F_{np-1}: F C and C F^T take the panels last to first
-    const bool notrans = op == Op::NoTrans;
-    const bool descending = (side == Side::Left) == notrans;
-    const Op lop = notrans ? Op::NoTrans : Op::ConjTrans;
-    Work<R> Vt(c.dev() ? Target::Devices : Target::Host, q ? size_t(1) : size_t(n) * nb);
-    for (int64_t t = 0; t < np; ++t) {
-        const int64_t j0 = (descending ? np - 1 - t : t) * nb;
-        const int64_t kb = std::min(nb, nref - j0), o = q ? j0 : j0 + 1, mv = order - o;
-        R const* V = A + o + j0 * lda;
-        int64_t ldv = lda;
-        if (!q) {
-            // the transposed row block A(j0:j0+kb, j0+1:n), explicit
-            if (c.dev()) {
-                kd::gebrd_form_vt<R>(mv, int(kb), A + j0 + o * lda, lda, Vt.data(), mv, c.stream);
-            } else {
-                for (int64_t k = 0; k < kb; ++k)
-                    for (int64_t j = 0; j < mv; ++j) Vt.data()[j + k * mv] = A[(j0 + k) + (o + j) * lda];
-            }
-            V = Vt.data();
-            ldv = mv;
+    Work<R> Vt(c.dev() ? Target::Devices : Target::Host, q || nref <= 0 ? size_t(1) : size_t(n) * nb);
+    apply_panel_reflectors<R>(c, side, op, nref, q ? 0 : 1, [&](int64_t j0, int64_t kb, int64_t& ldv) -> R const* {
+        if (q) {
+            ldv = lda;
+            return A + j0 + j0 * lda;
         }
-        if (side == Side::Left) lb::larfb(c, side, lop, mc - o, nc, kb, V, ldv, Tfac + j0 * nb, nb, C + o, ldc);
-        else lb::larfb(c, side, lop, mc, nc - o, kb, V, ldv, Tfac + j0 * nb, nb, C + o * ldc, ldc);
-    }
+        // the transposed row block A(j0:j0+kb, j0+1:n), explicit
+        ldv = n - j0 - 1;
+        form_vt<R>(c, ldv, kb, A + j0 + (j0 + 1) * lda, lda, Vt.data(), ldv);
+        return Vt.data();
+    }, Tfac, mc, nc, C, ldc);
 }
 
 #define SLATE_GEBRD_LOCAL_INST(R)                                                                                 \
@@ -260,25 +187,6 @@ void unmbr_gebrd_local(lb::Ctx const& c, Vect vect, Side side, Op op, int64_t m,
                                        R const*, int64_t, int64_t, R*, int64_t);
 SLATE_GEBRD_LOCAL_INST(float)
 SLATE_GEBRD_LOCAL_INST(double)
-
-template <typename T>
-void gebrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what) {
-    const std::string pre = std::string(who) + ": the one-stage bidiagonal reduction ";
-    if (is_complex_v<T>) slate_not_implemented(pre + "is implemented for real types only (" + what + " is complex)");
-    if (!A.storage()) return;
-    if (A.is_multi_device())
-        slate_not_implemented(pre + "runs on one device (" + what + " is a multi-device matrix)");
-    if (A.arbitrary_layout())
-        slate_not_implemented(pre + "needs a block-cyclic operand (" + what + " has a lambda layout)");
-    if (A.grid()->size() != 1)
-        slate_not_implemented(pre + "needs a grid of one process (" + what + " is distributed over " +
-                              std::to_string(A.grid()->size()) + "); distributed products are not implemented");
-}
-#define SLATE_GEBRD_CHECK_INST(T) template void gebrd_check_operand<T>(BaseMatrix<T> const&, char const*, char const*);
-SLATE_GEBRD_CHECK_INST(float)
-SLATE_GEBRD_CHECK_INST(double)
-SLATE_GEBRD_CHECK_INST(std::complex<float>)
-SLATE_GEBRD_CHECK_INST(std::complex<double>)
 
 }  // namespace internal
 
@@ -296,18 +204,8 @@ void gebrd(Matrix<T>& A, std::vector<real_type<T>>& D, std::vector<real_type<T>>
         slate_error_if_msg(A.op() != Op::NoTrans || !A.aligned(), "gebrd: a whole NoTrans matrix is required");
         const Target target = internal::resolve_target(opts);
         const int64_t m = A.m(), n = A.n(), nb = internal::kGebrdPanel;
-        const int64_t nn = std::max<int64_t>(n, 1);
-        TriangularFactors<T>* Ts[2] = {&TQ, &TP};
-        for (auto* Tx : Ts) {
-            Matrix<T> Tf(nb, nn, nb, nn, Grid::self()), tau(1, nn, 1, nn, Grid::self());
-            Tf.insertLocalTiles(target);
-            tau.insertLocalTiles(target);
-            set(T(0), T(0), Tf, opts);
-            set(T(0), T(0), tau, opts);
-            Tx->clear();
-            Tx->push_back(Tf);
-            Tx->push_back(tau);
-        }
+        TQ = internal::make_panel_factors<T>(n, nb, target, opts);
+        TP = internal::make_panel_factors<T>(n, nb, target, opts);
         D.assign(n, T(0));
         E.assign(std::max<int64_t>(n - 1, 0), T(0));
         if (n == 0) return;

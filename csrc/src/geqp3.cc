@@ -16,67 +16,24 @@
 // panel, the T factors S = V^T V plus the larft recurrence, the back-transform
 // one lb::larfb per panel.  The host target runs host::geqp3 (eig_host.cc),
 // the same algorithm in plain loops.
-#include "internal.hh"
-#include "slate_amd/eig_host.hh"
-#include "slate_amd/host_blas.hh"
-#include "../kernels/kernels.hh"
+#include "reduce_common.hh"
 
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <limits>
-#include <mutex>
 
 namespace slate {
 
 namespace {
-std::mutex g_stats_mu;
-Geqp3Stats g_stats;   // of the last factorization in this process
+internal::LastStats<Geqp3Stats> g_stats;   // of the last factorization in this process
 }  // namespace
 
-Geqp3Stats geqp3_stats() {
-    std::lock_guard<std::mutex> lk(g_stats_mu);
-    return g_stats;
-}
+Geqp3Stats geqp3_stats() { return g_stats.get(); }
 
 namespace internal {
 
 namespace {
-
-/// SLATE_GEQP3_PROFILE=1: events between the kernels of the device
-/// factorization, summed per kind into Geqp3Stats::ms_* after the final
-/// synchronisation (no extra synchronisation; the records cost a few
-/// microseconds each, so the profile is for the split, not for the total).
-struct Geqp3Profile {
-    enum Kind { Start = -1, Pivot = 0, Panel = 1, Product = 2, Gemm = 3, Larft = 4 };
-    bool on = false;
-    hipStream_t s = nullptr;
-    std::vector<std::pair<hipEvent_t, int>> ev;
-    Geqp3Profile(hipStream_t st) : s(st) {
-        const char* e = std::getenv("SLATE_GEQP3_PROFILE");
-        on = e && std::atoi(e) != 0;
-    }
-    void mark(int kind) {   // the interval that ends here is of this kind
-        if (!on) return;
-        hipEvent_t x;
-        slate_hip_call(hipEventCreate(&x));
-        slate_hip_call(hipEventRecord(x, s));
-        ev.push_back({x, kind});
-    }
-    void finish(Geqp3Stats& st) {   // after the stream was synchronised
-        double ms[5] = {0, 0, 0, 0, 0};
-        for (size_t k = 1; k < ev.size(); ++k) {
-            float t = 0;
-            slate_hip_call(hipEventElapsedTime(&t, ev[k - 1].first, ev[k].first));
-            if (ev[k].second >= 0) ms[ev[k].second] += t;
-        }
-        for (auto& x : ev) slate_hip_call(hipEventDestroy(x.first));
-        ev.clear();
-        st.ms_pivot = ms[Pivot]; st.ms_panel = ms[Panel]; st.ms_product = ms[Product]; st.ms_gemm = ms[Gemm];
-        st.ms_larft = ms[Larft];
-    }
-};
-
+/// SLATE_GEQP3_PROFILE=1 (StageProfile): the kinds of Geqp3Stats::ms_*
+enum Geqp3Kind { Pivot = 0, Panel = 1, Product = 2, Gemm = 3, Larft = 4, Kinds = 5 };
 }  // namespace
 
 template <typename R>
@@ -88,20 +45,21 @@ void geqp3_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
     for (int64_t j = 0; j < n; ++j) jpvt[j] = j;
     Geqp3Stats st;
     if (kmin == 0) {
-        std::lock_guard<std::mutex> lk(g_stats_mu);
-        g_stats = st;
+        g_stats.set(st);
         return;
     }
+    // T factors: every panel's reflectors are final (later panels touch A(k1:, k1:) only)
+    auto t_factors = [&](R* Vx) {
+        for (int64_t j0 = 0; j0 < kmin; j0 += nb)
+            panel_T_factors<R>(c, m - j0, std::min(nb, kmin - j0), A + j0 + j0 * lda, lda, tau + j0, Tfac + j0 * nb, nb,
+                               Vx);
+    };
     if (!c.dev()) {
         st.norm_recomputes = host::geqp3<R>(m, n, A, lda, jpvt.data(), tau, nb);
-        for (int64_t j0 = 0; j0 < kmin; j0 += nb) {
-            const int64_t kb = std::min(nb, kmin - j0);
-            host::larft<R>(m - j0, kb, A + j0 + j0 * lda, lda, tau + j0, Tfac + j0 * nb, nb);
-            ++st.panels;
-            st.columns += kb;
-        }
-        std::lock_guard<std::mutex> lk(g_stats_mu);
-        g_stats = st;
+        t_factors(nullptr);
+        st.panels = (kmin + nb - 1) / nb;
+        st.columns = kmin;
+        g_stats.set(st);
         return;
     }
     slate_error_if_msg(n >= (int64_t(1) << 31), "geqp3: more than 2^31 - 1 columns");
@@ -127,11 +85,11 @@ void geqp3_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
     wk.piv = ints.data() + 2 * n;
     wk.flag = reinterpret_cast<int*>(ints.data() + 2 * n + 1);
     wk.tol3z = std::sqrt(std::numeric_limits<R>::epsilon() / 2);
-    Geqp3Profile prof(s);
-    prof.mark(Geqp3Profile::Start);
+    StageProfile prof("SLATE_GEQP3_PROFILE", Kinds, s);
+    prof.mark(StageProfile::Start);
     kd::geqp3_norms<R>(m, n, A, lda, wk, s);
     ++st.launches_norms;
-    prof.mark(Geqp3Profile::Panel);
+    prof.mark(Panel);
     for (int64_t j0 = 0; j0 < kmin; j0 += nb) {
         const int64_t kb = std::min(nb, kmin - j0), k1 = j0 + kb;
         {
@@ -142,22 +100,22 @@ void geqp3_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
                     kd::geqp3_swap<R>(m, j, j0, A, lda, wk, s);
                     ++st.launches_pivot;
                     ++st.launches_swap;
-                    prof.mark(Geqp3Profile::Pivot);
+                    prof.mark(Pivot);
                 }
                 kd::geqp3_column<R>(m, j, j0, A, lda, wk, s);
                 kd::geqp3_larfg<R>(m, j, A, lda, wk, s);
                 ++st.launches_column;
                 ++st.launches_larfg;
-                prof.mark(Geqp3Profile::Panel);
+                prof.mark(Panel);
                 if (j + 1 >= n) break;
                 kd::geqp3_product<R>(m, n, j, j0, A, lda, wk, s);
-                prof.mark(Geqp3Profile::Product);
+                prof.mark(Product);
                 kd::geqp3_finish<R>(m, n, j, j0, A, lda, wk, s);
                 kd::geqp3_recompute<R>(m, n, j, j0, A, lda, wk, s);
                 ++st.launches_product;
                 ++st.launches_finish;
                 ++st.launches_recompute;
-                prof.mark(Geqp3Profile::Panel);
+                prof.mark(Panel);
             }
         }
         st.columns += kb;
@@ -166,22 +124,14 @@ void geqp3_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
             trace::Block tu("geqp3_gemm");
             lb::gemm(c, Op::NoTrans, Op::Trans, m - k1, n - k1, kb, R(-1), A + k1 + j0 * lda, lda, wk.F + k1, wk.ldf,
                      R(1), A + k1 + k1 * lda, lda);
-            prof.mark(Geqp3Profile::Gemm);
+            prof.mark(Gemm);
         }
     }
     {
-        // T factors: every panel's reflectors are final (later panels touch A(k1:, k1:) only)
         trace::Block tt("geqp3_larft");
         Work<R> Vx(Target::Devices, size_t(m) * nb);
-        for (int64_t j0 = 0; j0 < kmin; j0 += nb) {
-            const int64_t kb = std::min(nb, kmin - j0), mv = m - j0;
-            R* Tq = Tfac + j0 * nb;
-            lb::form_v(c, mv, kb, A + j0 + j0 * lda, lda, Vx.data(), mv);
-            lb::gemm_splitk(c, Op::Trans, Op::NoTrans, kb, kb, mv, std::max<int64_t>(1, std::min<int64_t>(32, mv / 512)),
-                            R(1), Vx.data(), mv, Vx.data(), mv, R(0), Tq, nb);
-            kd::larft_small<R>(int(kb), tau + j0, Tq, nb, s);
-        }
-        prof.mark(Geqp3Profile::Larft);
+        t_factors(Vx.data());
+        prof.mark(Larft);
     }
     // jpvt and the counters, contiguous on the device: one copy
     std::vector<int64_t> both(size_t(2 * n));
@@ -190,29 +140,20 @@ void geqp3_local(lb::Ctx const& c, int64_t m, int64_t n, R* A, int64_t lda, std:
     st.host_syncs = 1;
     std::copy(both.begin(), both.begin() + n, jpvt.begin());
     for (int64_t j = 0; j < n; ++j) st.norm_recomputes += both[n + j];
-    prof.finish(st);
-    std::lock_guard<std::mutex> lk(g_stats_mu);
-    g_stats = st;
+    const std::vector<double> ms = prof.finish();
+    st.ms_pivot = ms[Pivot]; st.ms_panel = ms[Panel]; st.ms_product = ms[Product]; st.ms_gemm = ms[Gemm];
+    st.ms_larft = ms[Larft];
+    g_stats.set(st);
 }
 
 template <typename R>
 void unmqr_geqp3_local(lb::Ctx const& c, Side side, Op op, int64_t m, int64_t n, R const* A, int64_t lda,
                        R const* Tfac, int64_t mc, int64_t nc, R* C, int64_t ldc) {
-    const int64_t nb = kGeqp3Panel, nref = std::min(m, n);
     slate_error_if_msg((side == Side::Left ? mc : nc) != m, "unmqr_geqp3: C does not match Q");
-    if (nref <= 0 || mc <= 0 || nc <= 0) return;
-    const int64_t np = (nref + nb - 1) / nb;
-    // Q = Q_0 Q_1 .. Q_{np-1}: Q C and C Q^T take the panels last to first
-    const bool notrans = op == Op::NoTrans;
-    const bool descending = (side == Side::Left) == notrans;
-    const Op lop = notrans ? Op::NoTrans : Op::ConjTrans;
-    for (int64_t t = 0; t < np; ++t) {
-        const int64_t j0 = (descending ? np - 1 - t : t) * nb;
-        const int64_t kb = std::min(nb, nref - j0);
-        R const* V = A + j0 + j0 * lda;
-        if (side == Side::Left) lb::larfb(c, side, lop, mc - j0, nc, kb, V, lda, Tfac + j0 * nb, nb, C + j0, ldc);
-        else lb::larfb(c, side, lop, mc, nc - j0, kb, V, lda, Tfac + j0 * nb, nb, C + j0 * ldc, ldc);
-    }
+    apply_panel_reflectors<R>(c, side, op, std::min(m, n), 0, [&](int64_t j0, int64_t, int64_t& ldv) {
+        ldv = lda;
+        return A + j0 + j0 * lda;
+    }, Tfac, mc, nc, C, ldc);
 }
 
 #define SLATE_GEQP3_LOCAL_INST(R)                                                                                  \
@@ -221,25 +162,6 @@ void unmqr_geqp3_local(lb::Ctx const& c, Side side, Op op, int64_t m, int64_t n,
                                        int64_t, int64_t, R*, int64_t);
 SLATE_GEQP3_LOCAL_INST(float)
 SLATE_GEQP3_LOCAL_INST(double)
-
-template <typename T>
-void geqp3_check_operand(BaseMatrix<T> const& A, char const* who, char const* what) {
-    const std::string pre = std::string(who) + ": the QR factorization with column pivoting ";
-    if (is_complex_v<T>) slate_not_implemented(pre + "is implemented for real types only (" + what + " is complex)");
-    if (!A.storage()) return;
-    if (A.is_multi_device())
-        slate_not_implemented(pre + "runs on one device (" + what + " is a multi-device matrix)");
-    if (A.arbitrary_layout())
-        slate_not_implemented(pre + "needs a block-cyclic operand (" + what + " has a lambda layout)");
-    if (A.grid()->size() != 1)
-        slate_not_implemented(pre + "needs a grid of one process (" + what + " is distributed over " +
-                              std::to_string(A.grid()->size()) + "); the distributed pivot search is not implemented");
-}
-#define SLATE_GEQP3_CHECK_INST(T) template void geqp3_check_operand<T>(BaseMatrix<T> const&, char const*, char const*);
-SLATE_GEQP3_CHECK_INST(float)
-SLATE_GEQP3_CHECK_INST(double)
-SLATE_GEQP3_CHECK_INST(std::complex<float>)
-SLATE_GEQP3_CHECK_INST(std::complex<double>)
 
 }  // namespace internal
 
@@ -253,15 +175,7 @@ void geqp3(Matrix<T>& A, std::vector<int64_t>& jpvt, TriangularFactors<T>& T_, O
         slate_error_if_msg(A.op() != Op::NoTrans || !A.aligned(), "geqp3: a whole NoTrans matrix is required");
         const Target target = internal::resolve_target(opts);
         const int64_t m = A.m(), n = A.n(), nb = internal::kGeqp3Panel;
-        const int64_t nn = std::max<int64_t>(n, 1);
-        Matrix<T> Tf(nb, nn, nb, nn, Grid::self()), tau(1, nn, 1, nn, Grid::self());
-        Tf.insertLocalTiles(target);
-        tau.insertLocalTiles(target);
-        set(T(0), T(0), Tf, opts);
-        set(T(0), T(0), tau, opts);
-        T_.clear();
-        T_.push_back(Tf);
-        T_.push_back(tau);
+        T_ = internal::make_panel_factors<T>(n, nb, target, opts);
         if (m == 0 || n == 0) {
             // nothing to factor and no launch: jpvt = identity, the counters cleared
             internal::geqp3_local<T>(lb::Ctx::host(), m, n, nullptr, 1, jpvt, nullptr, nullptr);

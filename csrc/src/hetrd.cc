@@ -10,26 +10,15 @@
 // updates are lb::syr2k, the T factors S = V^T V plus the larft recurrence, the
 // back-transform one lb::larfb per panel.  The host target runs host::hetrd
 // (eig_host.cc), the same algorithm in plain loops.
-#include "internal.hh"
-#include "slate_amd/eig_host.hh"
-#include "slate_amd/host_blas.hh"
-#include "../kernels/kernels.hh"
-
-#include <algorithm>
-#include <cstdlib>
-#include <mutex>
+#include "reduce_common.hh"
 
 namespace slate {
 
 namespace {
-std::mutex g_stats_mu;
-HetrdStats g_stats;   // of the last reduction in this process
+internal::LastStats<HetrdStats> g_stats;   // of the last reduction in this process
 }  // namespace
 
-HetrdStats hetrd_stats() {
-    std::lock_guard<std::mutex> lk(g_stats_mu);
-    return g_stats;
-}
+HetrdStats hetrd_stats() { return g_stats.get(); }
 
 namespace lb {
 
@@ -57,40 +46,8 @@ template void symv_lower<double>(Ctx const&, int64_t, double const*, int64_t, do
 namespace internal {
 
 namespace {
-
-/// SLATE_HETRD_PROFILE=1: events between the kernels of the device reduction,
-/// summed per kind into HetrdStats::ms_* after the final synchronisation (no
-/// extra synchronisation; the records cost a few microseconds each, so the
-/// profile is for the split, not for the total).
-struct HetrdProfile {
-    enum Kind { Start = -1, Panel = 0, Symv = 1, Syr2k = 2, Larft = 3 };
-    bool on = false;
-    hipStream_t s = nullptr;
-    std::vector<std::pair<hipEvent_t, int>> ev;
-    HetrdProfile(hipStream_t st) : s(st) {
-        const char* e = std::getenv("SLATE_HETRD_PROFILE");
-        on = e && std::atoi(e) != 0;
-    }
-    void mark(int kind) {   // the interval that ends here is of this kind
-        if (!on) return;
-        hipEvent_t x;
-        slate_hip_call(hipEventCreate(&x));
-        slate_hip_call(hipEventRecord(x, s));
-        ev.push_back({x, kind});
-    }
-    void finish(HetrdStats& st) {   // after the stream was synchronised
-        double ms[4] = {0, 0, 0, 0};
-        for (size_t k = 1; k < ev.size(); ++k) {
-            float t = 0;
-            slate_hip_call(hipEventElapsedTime(&t, ev[k - 1].first, ev[k].first));
-            if (ev[k].second >= 0) ms[ev[k].second] += t;
-        }
-        for (auto& x : ev) slate_hip_call(hipEventDestroy(x.first));
-        ev.clear();
-        st.ms_panel = ms[Panel]; st.ms_symv = ms[Symv]; st.ms_syr2k = ms[Syr2k]; st.ms_larft = ms[Larft];
-    }
-};
-
+/// SLATE_HETRD_PROFILE=1 (StageProfile): the kinds of HetrdStats::ms_*
+enum HetrdKind { Panel = 0, Symv = 1, Syr2k = 2, Larft = 3, Kinds = 4 };
 }  // namespace
 
 template <typename R>
@@ -102,18 +59,20 @@ void hetrd_local(lb::Ctx const& c, int64_t n, R* A, int64_t lda, std::vector<R>&
     e.assign(std::max<int64_t>(n - 1, 0), R(0));
     if (n == 0) return;
     HetrdStats st;
+    // T factors: every panel's V is final (later panels touch A(k1:, k1:) only)
+    auto t_factors = [&](R* Vx) {
+        for (int64_t j0 = 0; j0 < n - 1; j0 += nb)
+            panel_T_factors<R>(c, n - j0 - 1, std::min(nb, n - 1 - j0), A + (j0 + 1) + j0 * lda, lda, tau + j0,
+                               Tfac + j0 * nb, nb, Vx);
+    };
     if (!c.dev()) {
         std::vector<R> eh(n, R(0));
         host::hetrd<R>(n, A, lda, d.data(), eh.data(), tau, nb);
         std::copy(eh.begin(), eh.begin() + (n - 1), e.begin());
-        for (int64_t j0 = 0; j0 < n - 1; j0 += nb) {
-            const int64_t kb = std::min(nb, n - 1 - j0);
-            host::larft<R>(n - j0 - 1, kb, A + (j0 + 1) + j0 * lda, lda, tau + j0, Tfac + j0 * nb, nb);
-            ++st.panels;
-            st.columns += kb;
-        }
-        std::lock_guard<std::mutex> lk(g_stats_mu);
-        g_stats = st;
+        t_factors(nullptr);
+        st.panels = (n - 1 + nb - 1) / nb;
+        st.columns = n - 1;
+        g_stats.set(st);
         return;
     }
     hipStream_t s = c.stream;
@@ -134,8 +93,8 @@ void hetrd_local(lb::Ctx const& c, int64_t n, R* A, int64_t lda, std::vector<R>&
     wk.tau = tau;
     wk.rowpart = part.data();
     wk.colpart = part.data() + size_t(n / 16 + 2) * n;
-    HetrdProfile prof(s);
-    prof.mark(HetrdProfile::Start);
+    StageProfile prof("SLATE_HETRD_PROFILE", Kinds, s);
+    prof.mark(StageProfile::Start);
     for (int64_t j0 = 0; j0 < n - 1; j0 += nb) {
         const int64_t kb = std::min(nb, n - 1 - j0), k1 = j0 + kb;
         {
@@ -143,13 +102,13 @@ void hetrd_local(lb::Ctx const& c, int64_t n, R* A, int64_t lda, std::vector<R>&
             for (int64_t i = j0; i < k1; ++i) {
                 kd::hetrd_column<R>(n, i, j0, true, A, lda, wk, s);
                 kd::hetrd_larfg<R>(n, i, A, lda, wk, s);
-                prof.mark(HetrdProfile::Panel);
+                prof.mark(Panel);
                 kd::hetrd_symv<R>(n, i, j0, A, lda, wk, s);
-                prof.mark(HetrdProfile::Symv);
+                prof.mark(Symv);
                 kd::hetrd_correct<R>(n, i, j0, A, lda, wk, s);
             }
             kd::hetrd_column<R>(n, k1, j0, false, A, lda, wk, s);   // last column of W
-            prof.mark(HetrdProfile::Panel);
+            prof.mark(Panel);
         }
         st.launches_column += kb + 1;
         st.launches_larfg += kb;
@@ -160,53 +119,32 @@ void hetrd_local(lb::Ctx const& c, int64_t n, R* A, int64_t lda, std::vector<R>&
         trace::Block tu("hetrd_syr2k");
         lb::syr2k(c, Uplo::Lower, Op::NoTrans, n - k1, kb, R(-1), A + k1 + j0 * lda, lda, wk.W + k1, wk.ldw, R(1),
                   A + k1 + k1 * lda, lda);
-        prof.mark(HetrdProfile::Syr2k);
+        prof.mark(Syr2k);
     }
     device::memcpy_async(wk.d + (n - 1), A + (n - 1) + (n - 1) * lda, sizeof(R), s);
     {
-        // T factors: every panel's V is final (later panels touch A(k1:, k1:) only)
         trace::Block tt("hetrd_larft");
         Work<R> Vx(Target::Devices, size_t(n) * nb);
-        for (int64_t j0 = 0; j0 < n - 1; j0 += nb) {
-            const int64_t kb = std::min(nb, n - 1 - j0), mv = n - j0 - 1;
-            R* Tp = Tfac + j0 * nb;
-            lb::form_v(c, mv, kb, A + (j0 + 1) + j0 * lda, lda, Vx.data(), mv);
-            lb::gemm_splitk(c, Op::Trans, Op::NoTrans, kb, kb, mv, std::max<int64_t>(1, std::min<int64_t>(32, mv / 512)),
-                            R(1), Vx.data(), mv, Vx.data(), mv, R(0), Tp, nb);
-            kd::larft_small<R>(int(kb), tau + j0, Tp, nb, s);
-        }
-        prof.mark(HetrdProfile::Larft);
+        t_factors(Vx.data());
+        prof.mark(Larft);
     }
     device::memcpy_async(d.data(), wk.d, size_t(n) * sizeof(R), s);
     if (n > 1) device::memcpy_async(e.data(), wk.e, size_t(n - 1) * sizeof(R), s);
     slate_hip_call(hipStreamSynchronize(s));
     st.host_syncs = 1;
-    prof.finish(st);
-    std::lock_guard<std::mutex> lk(g_stats_mu);
-    g_stats = st;
+    const std::vector<double> ms = prof.finish();
+    st.ms_panel = ms[Panel]; st.ms_symv = ms[Symv]; st.ms_syr2k = ms[Syr2k]; st.ms_larft = ms[Larft];
+    g_stats.set(st);
 }
 
 template <typename R>
 void unmtr_hetrd_local(lb::Ctx const& c, Side side, Op op, int64_t n, R const* A, int64_t lda, R const* Tfac,
                        int64_t mc, int64_t nc, R* C, int64_t ldc) {
-    const int64_t nb = kHetrdPanel;
     slate_error_if_msg((side == Side::Left ? mc : nc) != n, "unmtr_hetrd: C does not match Q");
-    if (n < 2 || mc <= 0 || nc <= 0) return;
-    const int64_t np = (n - 1 + nb - 1) / nb;
-    // Q = Q_0 Q_1 .. Q_{np-1}: Q C and C Q^T take the panels last to first
-    const bool notrans = op == Op::NoTrans;
-    const bool descending = (side == Side::Left) == notrans;
-    for (int64_t t = 0; t < np; ++t) {
-        const int64_t j0 = (descending ? np - 1 - t : t) * nb;
-        const int64_t kb = std::min(nb, n - 1 - j0), o = j0 + 1;
-        R const* V = A + o + j0 * lda;
-        if (side == Side::Left)
-            lb::larfb(c, side, notrans ? Op::NoTrans : Op::ConjTrans, mc - o, nc, kb, V, lda, Tfac + j0 * nb, nb, C + o,
-                      ldc);
-        else
-            lb::larfb(c, side, notrans ? Op::NoTrans : Op::ConjTrans, mc, nc - o, kb, V, lda, Tfac + j0 * nb, nb,
-                      C + o * ldc, ldc);
-    }
+    apply_panel_reflectors<R>(c, side, op, n - 1, 1, [&](int64_t j0, int64_t, int64_t& ldv) {
+        ldv = lda;
+        return A + (j0 + 1) + j0 * lda;
+    }, Tfac, mc, nc, C, ldc);
 }
 
 #define SLATE_HETRD_LOCAL_INST(R)                                                                              \
@@ -215,25 +153,6 @@ void unmtr_hetrd_local(lb::Ctx const& c, Side side, Op op, int64_t n, R const* A
                                        int64_t, R*, int64_t);
 SLATE_HETRD_LOCAL_INST(float)
 SLATE_HETRD_LOCAL_INST(double)
-
-template <typename T>
-void hetrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what) {
-    const std::string pre = std::string(who) + ": the one-stage reduction ";
-    if (is_complex_v<T>) slate_not_implemented(pre + "is implemented for real types only (" + what + " is complex)");
-    if (!A.storage()) return;
-    if (A.is_multi_device())
-        slate_not_implemented(pre + "runs on one device (" + what + " is a multi-device matrix)");
-    if (A.arbitrary_layout())
-        slate_not_implemented(pre + "needs a block-cyclic operand (" + what + " has a lambda layout)");
-    if (A.grid()->size() != 1)
-        slate_not_implemented(pre + "needs a grid of one process (" + what + " is distributed over " +
-                              std::to_string(A.grid()->size()) + "); a distributed symv is not implemented");
-}
-#define SLATE_HETRD_CHECK_INST(T) template void hetrd_check_operand<T>(BaseMatrix<T> const&, char const*, char const*);
-SLATE_HETRD_CHECK_INST(float)
-SLATE_HETRD_CHECK_INST(double)
-SLATE_HETRD_CHECK_INST(std::complex<float>)
-SLATE_HETRD_CHECK_INST(std::complex<double>)
 
 }  // namespace internal
 
@@ -252,20 +171,12 @@ void hetrd(HermitianMatrix<T>& A, std::vector<real_type<T>>& D, std::vector<real
         Matrix<T> Ag(A);
         Ag.set_uplo(Uplo::General);
         slate_error_if_msg(!Ag.aligned(), "hetrd: a whole matrix is required");
-        Matrix<T> Tf(nb, std::max<int64_t>(n, 1), nb, std::max<int64_t>(n, 1), Grid::self());
-        Matrix<T> tau(1, std::max<int64_t>(n, 1), 1, std::max<int64_t>(n, 1), Grid::self());
-        Tf.insertLocalTiles(target);
-        tau.insertLocalTiles(target);
-        set(T(0), T(0), Tf, opts);
-        set(T(0), T(0), tau, opts);
-        T_.clear();
-        T_.push_back(Tf);
-        T_.push_back(tau);
+        T_ = internal::make_panel_factors<T>(n, nb, target, opts);
         D.assign(n, T(0));
         E.assign(std::max<int64_t>(n - 1, 0), T(0));
         if (n == 0) return;
         const Loc loc = internal::loc_of(target);
-        LocalBlock<T> la = Ag.local(loc, true), lt = Tf.local(loc, true), ltau = tau.local(loc, true);
+        LocalBlock<T> la = Ag.local(loc, true), lt = T_[0].local(loc, true), ltau = T_[1].local(loc, true);
         slate_error_if_msg(la.m != n || la.n != n || lt.ld != nb, "hetrd: unexpected local layout");
         lb::Ctx c = target == Target::Devices ? lb::Ctx::device(0) : lb::Ctx::host();
         internal::hetrd_local<T>(c, n, la.ptr, la.ld, D, E, ltau.ptr, lt.ptr);

@@ -308,9 +308,11 @@ template <typename T>
 void bdsdc_place(lb::Ctx const& c, Matrix<T>& A, real_type<T> const* src, int64_t lds, bool trans,
                  std::vector<T> const& phase);
 
-/// Panel width of the one-stage tridiagonal reduction (hetrd.cc); its T
-/// factors are kHetrdPanel x kHetrdPanel blocks, panel p at column p * kHetrdPanel.
-constexpr int64_t kHetrdPanel = 64;
+/// Panel width of the one-stage reductions (hetrd.cc, gebrd.cc, geqp3.cc; what
+/// they share is in reduce_common.hh, their operand checks among it); their T
+/// factors are kReducePanel x kReducePanel blocks, panel p at column p * kReducePanel.
+constexpr int64_t kReducePanel = 64;
+constexpr int64_t kHetrdPanel = kReducePanel, kGebrdPanel = kReducePanel, kGeqp3Panel = kReducePanel;
 /// One-stage tridiagonal reduction of the lower triangle of the contiguous
 /// local n x n array A (c's memory): A = Q T Q^T, T = tridiag(d, e) with
 /// signed e, reflectors left in A below the subdiagonal with their unit entry
@@ -325,17 +327,7 @@ void hetrd_local(lb::Ctx const& c, int64_t n, R* A, int64_t lda, std::vector<R>&
 template <typename R>
 void unmtr_hetrd_local(lb::Ctx const& c, Side side, Op op, int64_t n, R const* A, int64_t lda, R const* Tfac,
                        int64_t mc, int64_t nc, R* C, int64_t ldc);
-/// slate::NotImplemented unless the one-stage reduction can take this operand
-/// (real type, one process, one device, block-cyclic); `who` names the routine
-template <typename T>
-void hetrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
 
-/// gebrd's sibling of hetrd_check_operand: the same refusals, worded for the
-/// one-stage bidiagonal reduction
-template <typename T>
-void gebrd_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
-/// Panel width of the one-stage bidiagonal reduction (gebrd.cc); T factors as hetrd's.
-constexpr int64_t kGebrdPanel = 64;
 /// One-stage bidiagonal reduction of the contiguous local m x n array A (c's
 /// memory), m >= n: A = Q B P^T, B upper bidiagonal (d, e), left reflectors
 /// left in A below the diagonal and right ones right of the superdiagonal,
@@ -350,12 +342,6 @@ template <typename R>
 void unmbr_gebrd_local(lb::Ctx const& c, Vect vect, Side side, Op op, int64_t m, int64_t n, R const* A, int64_t lda,
                        R const* Tfac, int64_t mc, int64_t nc, R* C, int64_t ldc);
 
-/// geqp3's sibling of gebrd_check_operand: the same refusals, worded for the
-/// QR factorization with column pivoting
-template <typename T>
-void geqp3_check_operand(BaseMatrix<T> const& A, char const* who, char const* what);
-/// Panel width of the QR with column pivoting (geqp3.cc); T factors as gebrd's.
-constexpr int64_t kGeqp3Panel = 64;
 /// QR with column pivoting of the contiguous local m x n array A (c's memory):
 /// A P = Q R, R in the upper triangle / trapezoid, the min(m, n) reflectors
 /// below the diagonal with unit entries implied; tau (min(m, n)) and Tfac

@@ -19,15 +19,17 @@ sys.path.insert(0, HERE)
 import torch  # noqa: F401,E402  (HIP runtime first)
 import slate_d35_amd as s  # noqa: E402
 from slate_d35_amd import parallel  # noqa: E402
-from helpers import rnd  # noqa: E402
+from helpers import refusal_text, rnd  # noqa: E402
 
 
-def refused(fn):
+def refused(fn, text):
+    """fn raises slate::NotImplemented with this text, the grid's size (P Q = 2 here) named in it"""
     try:
         fn()
-    except Exception as ex:  # slate::NotImplemented
+    except Exception as ex:
         msg = str(ex)
         assert "grid of one process" in msg and "not implemented" in msg.lower(), msg
+        assert refusal_text(ex) == text, msg
         return True
     return False
 
@@ -37,8 +39,10 @@ def main():
     parallel.init_grid(p, q, transport=os.environ.get("SLATE_TRANSPORT", "auto"))
     n, nb = 96, 32
     a = rnd(n, n, np.float64, 4)
-    assert refused(lambda: s.svd_vals(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg, method_gebrd="one_stage"))
-    assert refused(lambda: s.gebrd(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg))
+    assert refused(lambda: s.svd_vals(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg, method_gebrd="one_stage"),
+                   f"svd: the one-stage bidiagonal reduction needs a grid of one process (A is distributed over {p * q}); distributed products are not implemented")  # noqa: E501
+    assert refused(lambda: s.gebrd(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg),
+                   f"gebrd: the one-stage bidiagonal reduction needs a grid of one process (A is distributed over {p * q}); distributed products are not implemented")  # noqa: E501
     w = s.svd_vals(s.from_numpy(a.copy(), nb=nb, target=tg), target=tg)
     ref = np.linalg.svd(a, compute_uv=False)
     assert np.abs(w - ref).max() <= 1e-10 * np.abs(ref).max()

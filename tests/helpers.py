@@ -1,3 +1,5 @@
+import re
+
 import numpy as np
 
 import slate_d35_amd as s
@@ -47,3 +49,10 @@ def butterfly_dense(n, depth, seed):
                 L[i + h, i], L[i + h, i + h] = s2 * R0, -s2 * R1
         W = L @ W
     return W
+
+
+def refusal_text(ex):
+    """The text of a slate::NotImplemented without the source location (function, file, line) it ends with."""
+    m = re.fullmatch(r"not yet implemented: (.*) in \w+ at \S+:\d+", str(ex), re.S)
+    assert m, str(ex)
+    return m.group(1)

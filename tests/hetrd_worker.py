@@ -19,15 +19,17 @@ sys.path.insert(0, HERE)
 import torch  # noqa: F401,E402  (HIP runtime first)
 import slate_d35_amd as s  # noqa: E402
 from slate_d35_amd import parallel  # noqa: E402
-from helpers import rnd  # noqa: E402
+from helpers import refusal_text, rnd  # noqa: E402
 
 
-def refused(fn):
+def refused(fn, text):
+    """fn raises slate::NotImplemented with this text, the grid's size (P Q = 2 here) named in it"""
     try:
         fn()
-    except Exception as ex:  # slate::NotImplemented
+    except Exception as ex:
         msg = str(ex)
         assert "grid of one process" in msg and "not implemented" in msg.lower(), msg
+        assert refusal_text(ex) == text, msg
         return True
     return False
 
@@ -39,8 +41,10 @@ def main():
     a = rnd(n, n, np.float64, 4)
     a = (a + a.T) / 2
     H = s.HermitianMatrix(s.Uplo.Lower, s.from_numpy(a, nb=nb, target=tg))
-    assert refused(lambda: s.heev(H, target=tg, method_hetrd="one_stage"))
-    assert refused(lambda: s.hetrd(H, target=tg))
+    assert refused(lambda: s.heev(H, target=tg, method_hetrd="one_stage"),
+                   f"heev: the one-stage reduction needs a grid of one process (A is distributed over {p * q}); a distributed symv is not implemented")  # noqa: E501
+    assert refused(lambda: s.hetrd(H, target=tg),
+                   f"hetrd: the one-stage reduction needs a grid of one process (A is distributed over {p * q}); a distributed symv is not implemented")  # noqa: E501
     w = s.heev(H, target=tg)
     ref = np.linalg.eigvalsh(a)
     assert np.abs(w - ref).max() <= 1e-10 * np.abs(ref).max()
