@@ -13,7 +13,7 @@ prototype, and maps C types onto iso_c_binding kinds:
   T* (data arrays, Lambda, Sigma)             -> assumed-size array T(*)
   int* / int64_t* (iteration count, nfound)   -> integer kinds by reference
   float* / double* (d, e, w of stebz / bdsbz) -> assumed-size array
-  int64_t* jpvt (column permutation)          -> assumed-size array
+  int64_t* jpvt (column permutation), ifail   -> assumed-size array
   const char* (matgen kind)                   -> character(kind=c_char) s(*)
   slate_Options const*                        -> type(slate_Options) opts(*)
 
@@ -89,7 +89,7 @@ def ftype(ctype, name, kinds):
             "uint64_t": ("integer(c_int64_t)", "c_int64_t"), "double": ("real(c_double)", "c_double"),
             "float": ("real(c_float)", "c_float")}[t]
     kinds.add(base[1])
-    if ptr and (t in ("float", "double") or name == "jpvt"):
+    if ptr and (t in ("float", "double") or name in ("jpvt", "ifail")):
         return f"{base[0]} :: {name}(*)"
     return f"{base[0]} :: {name}" if ptr else f"{base[0]}, value :: {name}"
 

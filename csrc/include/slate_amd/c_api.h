@@ -54,7 +54,7 @@ enum { slate_MethodSVD_QR = 81, slate_MethodSVD_DC = 68, slate_MethodSVD_Bisecti
  * vectors; Bisection: values only (Z NULL), Sturm-count bisection */
 enum { slate_MethodEig_QR = 81, slate_MethodEig_DC = 68, slate_MethodEig_Bisection = 66 };
 
-/* range of slate_stebz_* / slate_bdsbz_* (slate::Range) */
+/* range of slate_stebz_* / slate_bdsbz_* / slate_hermitian_eig_range_* (slate::Range) */
 typedef char slate_Range;    /* 'A' all, 'V' values in [vl, vu), 'I' indices il .. iu (1-based) */
 
 /* ivalue of slate_Option_GemmPrecision (slate::GemmPrecision): arithmetic of
@@ -174,6 +174,11 @@ int slate_least_squares_solve_##X(slate_Matrix_##X A, slate_Matrix_##X BX, int n
 /* eigenvalues / SVD: Lambda (n) and Sigma (min(m,n)) are real arrays; Z, U, VT may be NULL */            \
 int slate_hermitian_eig_##X(slate_Uplo uplo, slate_Matrix_##X A, real_t* Lambda, slate_Matrix_##X Z,      \
                             int nopts, slate_Options const* opts);                                        \
+/* eigenpairs of a range (slate::heevx): Lambda has room for n values (il .. iu: iu - il + 1 suffice), */  \
+/* *nfound receives their number m; Z (n rows, at least m columns) may be NULL: values only            */  \
+int slate_hermitian_eig_range_##X(slate_Uplo uplo, slate_Matrix_##X A, slate_Range range, real_t vl,       \
+                                  real_t vu, int64_t il, int64_t iu, int64_t* nfound, real_t* Lambda,      \
+                                  slate_Matrix_##X Z, int nopts, slate_Options const* opts);               \
 int slate_svd_##X(slate_Matrix_##X A, real_t* Sigma, slate_Matrix_##X U, slate_Matrix_##X VT, int nopts,  \
                   slate_Options const* opts);                                                             \
 /* auxiliary */                                                                                            \
@@ -221,6 +226,17 @@ int slate_bdsbz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t i
                     float const* e, int64_t* nfound, float* s, int nopts, slate_Options const* opts);
 int slate_bdsbz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
                     double const* e, int64_t* nfound, double* s, int nopts, slate_Options const* opts);
+
+/* Inverse iteration on plain arrays (slate::stein): the unit eigenvectors of
+ * the symmetric tridiagonal (d of n, e of n - 1) for the m ascending
+ * eigenvalues w, as slate_stebz_* returns them, into the column-major z with
+ * leading dimension ldz >= n.  *nfailed (may be NULL) receives the number of
+ * vectors that were not accepted, ifail (may be NULL, room for m) their
+ * 1-based indices.  Returns 0, or -1 (slate_last_error). */
+int slate_stein_r32(int64_t n, float const* d, float const* e, int64_t m, float const* w, float* z, int64_t ldz,
+                    int64_t* nfailed, int64_t* ifail, int nopts, slate_Options const* opts);
+int slate_stein_r64(int64_t n, double const* d, double const* e, int64_t m, double const* w, double* z, int64_t ldz,
+                    int64_t* nfailed, int64_t* ifail, int nopts, slate_Options const* opts);
 
 /* QR with column pivoting, real types (slate::geqp3 / unmqr_geqp3 / gelsy).
  * jpvt has room for n entries and is 0-based: column j of A P is column

@@ -79,6 +79,14 @@ void sturm_counts(int64_t n, const R* d, const R* e2, R pivmin, int64_t nx, cons
 template <typename R>
 int64_t stebz_range(int64_t n, const R* d, const R* e2, R pivmin, R lo, R hi, R abstol, R floor, int64_t k0,
                     int64_t k1, R* w);
+/// Host twin of kernels/stein.hip over slate_amd/stein.hh: unit eigenvectors
+/// of the scaled tridiagonal (d, e), |T|_1 = onenrm, for the m scaled values w
+/// with the clusters of invit::find_clusters, into Z (n x m, column-major).
+/// Five rounds, OpenMP across vectors and across clusters; done[j] = 1 for a
+/// vector that passed the growth test three times.
+template <typename R>
+void stein(int64_t n, const R* d, const R* e, R onenrm, int64_t m, const R* w, const int32_t* cluster,
+           int64_t nclusters, const int64_t* first, const int64_t* last, R* Z, int64_t ldz, int32_t* done);
 
 /// Divide and conquer: eigenvalues ascending in d, eigenvectors in Q (n x n).
 template <typename R>

@@ -304,6 +304,17 @@ template <typename T>
 void eig(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {}) {
     heev(A, Lambda, Z, opts);
 }
+/// The eigenpairs of a range (heevx / syevx); returns their number.
+template <typename T>
+int64_t eig_range(HermitianMatrix<T>& A, Range range, real_type<T> vl, real_type<T> vu, int64_t il, int64_t iu,
+                  std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {}) {
+    return heevx(A, range, vl, vu, il, iu, Lambda, Z, opts);
+}
+template <typename T>
+int64_t eig_range(SymmetricMatrix<T>& A, Range range, real_type<T> vl, real_type<T> vu, int64_t il, int64_t iu,
+                  std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {}) {
+    return syevx(A, range, vl, vu, il, iu, Lambda, Z, opts);
+}
 template <typename T>
 void eig_vals(SymmetricMatrix<T>& A, std::vector<real_type<T>>& Lambda, Options const& opts = {}) {
     Matrix<T> Z;

@@ -207,6 +207,20 @@ int64_t cholqr(Matrix<T>& A, Matrix<T>& R, Options const& opts = {});
 // Eigenvalues / SVD (host-centric, reference heev.cc / svd.cc)
 template <typename T>
 void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {});
+/// Eigenpairs of a subset: the eigenvalues of the range (the semantics of
+/// stebz: Range::All, Range::Value [vl, vu), Range::Index 1 <= il <= iu <= n)
+/// ascending in Lambda, sized to their number m, which is returned, and when
+/// Z is wanted (n rows, at least m columns) their orthonormal eigenvectors in
+/// its first m columns, the others zero.  The reduction that
+/// Option::MethodHetrd selects, stebz on the tridiagonal, stein for the
+/// vectors and the back-transforms of heev on the n x m block only.  A is not
+/// modified.  A Z with fewer than m columns throws Exception naming m, with
+/// Lambda already filled.  Real and complex types on the two-stage reduction,
+/// real types on the one-stage one.  One process, one device, block-cyclic
+/// operands: anything else throws NotImplemented.
+template <typename T>
+int64_t heevx(HermitianMatrix<T>& A, Range range, real_type<T> vl, real_type<T> vu, int64_t il, int64_t iu,
+              std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {});
 template <typename T>
 void svd(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Matrix<T>& VT, Options const& opts = {});
 /// Stage 1 of heev: Hermitian (dense general storage) -> band of width nb.
@@ -365,6 +379,39 @@ struct StebzStats {
     int64_t n = 0, values = 0, points = 0, steps = 0, launches = 0, host_syncs = 0;
 };
 StebzStats stebz_stats();
+/// Eigenvectors of the symmetric tridiagonal (D of n, E of n - 1) that belong
+/// to the m eigenvalues W, ascending as stebz returns them, by inverse
+/// iteration (src/stein.cc, slate_amd/stein.hh): Z becomes the n x m
+/// column-major matrix of unit vectors, one column per value, the entry of
+/// largest modulus positive.  Values closer than 1e-3 |T|_1 form a cluster,
+/// whose vectors are orthonormalised against each other (classical
+/// Gram-Schmidt applied twice) after every round; there are exactly five
+/// rounds (LAPACK's MAXITS).  A vector is accepted when it passes LAPACK's
+/// growth test in three of them; returns the number that were not, their
+/// 1-based indices in ifail (LAPACK's ifail).  Target::Devices: the launches
+/// depend on n, m and the existence of a cluster only, one host
+/// synchronisation, two calls give the same bits; host targets: the same
+/// arithmetic with OpenMP across vectors and clusters.  n = 0 or m = 0
+/// returns at once, n = 1 returns [1], an all-zero matrix the first m unit
+/// vectors, all without a launch.  Throws Exception, before any launch, on a
+/// non-finite entry of D, E or W, on a W that is not ascending and on m > n.
+template <typename R>
+int64_t stein(std::vector<R> const& D, std::vector<R> const& E, std::vector<R> const& W, std::vector<R>& Z,
+              Options const& opts = {});
+template <typename R>
+int64_t stein(std::vector<R> const& D, std::vector<R> const& E, std::vector<R> const& W, std::vector<R>& Z,
+              std::vector<int64_t>& ifail, Options const& opts = {});
+/// Counters of the last stein of this process (also through heevx): order,
+/// vectors, clusters and the size of the largest, rounds run, vectors not
+/// accepted, kernel launches and host synchronisations (both zero on the host
+/// target).  With SLATE_STEIN_PROFILE=1 in the environment, the milliseconds
+/// of the device kernels by kind (events, no extra synchronisation).
+struct SteinStats {
+    int64_t n = 0, values = 0, clusters = 0, largest_cluster = 0, rounds = 0, failed = 0, launches = 0,
+            host_syncs = 0;
+    double ms_solve = 0, ms_orth = 0, ms_transpose = 0;
+};
+SteinStats stein_stats();
 /// Tridiagonal QL/QR; with jobz = Vec, Z := Z * (eigenvectors).
 template <typename T>
 void steqr2(Job jobz, std::vector<real_type<T>>& D, std::vector<real_type<T>>& E, Matrix<T>& Z,
@@ -523,6 +570,10 @@ Geqp3Stats geqp3_stats();
 // Real-symmetric aliases (real types only) and compatibility names.
 template <typename T>
 void syev(SymmetricMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {});
+/// syevx: heevx for a real SymmetricMatrix.
+template <typename T>
+int64_t syevx(SymmetricMatrix<T>& A, Range range, real_type<T> vl, real_type<T> vu, int64_t il, int64_t iu,
+              std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts = {});
 template <typename T>
 void sygst(int64_t itype, SymmetricMatrix<T>& A, SymmetricMatrix<T> const& B, Options const& opts = {});
 template <typename T>

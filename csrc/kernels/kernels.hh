@@ -14,6 +14,7 @@
 #include "dev_types.hh"
 #include "matgen_entry.hh"
 #include "slate_amd/secular.hh"
+#include "slate_amd/stein.hh"
 #include "slate_amd/sturm.hh"
 
 namespace slate_amd {
@@ -211,6 +212,42 @@ struct StebzRefine {
 /// max_values: k1 - k0, or with cnt the most it can be (n - kmin)
 template <typename R>
 void stebz_refine(StebzRefine<R> const& a, int64_t max_values, hipStream_t s);
+
+// ---- inverse iteration (stein.hip), float and double; arithmetic of slate_amd/stein.hh
+/// One round of every unfinished vector.  d, e, w: the scaled tridiagonal and
+/// the m scaled values; x, ua, ub, ud: workspaces [row][vector] of n x mp
+/// reals, mp = m rounded up to the wave (kSteinLanes); the rest per vector.
+constexpr int kSteinLanes = 64;
+template <typename R>
+struct SteinSolve {
+    int64_t n = 0, m = 0, mp = 0;
+    const R *d = nullptr, *e = nullptr, *w = nullptr;
+    R bnorm = 0;                         // |b|_inf of every right-hand side
+    const int32_t* cluster = nullptr;    // cluster of a vector or -1
+    R *x = nullptr, *ua = nullptr, *ub = nullptr, *ud = nullptr;
+    R *xmax = nullptr, *nrm = nullptr, *unn = nullptr;   // largest entry (signed) and 2-norm of x; u_nn
+    int32_t *pass = nullptr, *done = nullptr;
+    int round = 0;                       // 0: the right-hand side is the start vector
+};
+template <typename R>
+void stein_solve(SteinSolve<R> const& a, hipStream_t s);
+/// Orthonormalises the columns first[c] .. last[c] of x, one workgroup per
+/// cluster c, and judges the cluster (cpass: its passes so far).
+template <typename R>
+struct SteinOrth {
+    int64_t n = 0, mp = 0;
+    const int64_t *first = nullptr, *last = nullptr;
+    R* x = nullptr;
+    R *xmax = nullptr, *nrm = nullptr;
+    const R* unn = nullptr;
+    int32_t *cpass = nullptr, *done = nullptr;
+};
+template <typename R>
+void stein_orth(SteinOrth<R> const& a, int64_t clusters, hipStream_t s);
+/// Z (n x m, column-major) = the columns of x scaled to unit norm, largest entry positive
+template <typename R>
+void stein_transpose(int64_t n, int64_t m, int64_t mp, const R* x, const R* xmax, const R* nrm, R* Z, int64_t ldz,
+                     hipStream_t s);
 
 // ---- shared by the one-stage reductions (reduce_tiles.hh, larfg_vec.hip), float and double
 /// columns of a panel of hetrd, gebrd and geqp3: the kernels size their LDS

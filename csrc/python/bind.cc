@@ -728,6 +728,44 @@ PYBIND11_MODULE(_slate, m) {
         }
         return py::array_t<float>(py::ssize_t(w.size()), w.data());
     });
+    m.def("stein_stats", []() {
+        const SteinStats st = stein_stats();
+        py::dict r;
+        r["n"] = st.n;
+        r["values"] = st.values;
+        r["clusters"] = st.clusters;
+        r["largest_cluster"] = st.largest_cluster;
+        r["rounds"] = st.rounds;
+        r["failed"] = st.failed;
+        r["launches"] = st.launches;
+        r["host_syncs"] = st.host_syncs;
+        r["ms_solve"] = st.ms_solve;
+        r["ms_orth"] = st.ms_orth;
+        r["ms_transpose"] = st.ms_transpose;
+        return r;
+    });
+    // inverse iteration on plain vectors: type "s" or "d"; returns (Z n x m, ifail)
+    m.def("stein", [](std::string type, std::vector<double> d, std::vector<double> e, std::vector<double> w,
+                      py::dict opts) -> py::object {
+        if (type != "d" && type != "s") throw Exception("stein: float32 or float64");
+        const Options o = to_options(opts);
+        const py::ssize_t n = py::ssize_t(d.size()), mm = py::ssize_t(w.size());
+        std::vector<int64_t> ifail;
+        auto shaped = [&](auto const& z) {
+            using X = std::decay_t<decltype(z[0])>;
+            py::array_t<X, py::array::f_style> out({n, mm});
+            if (!z.empty()) std::memcpy(out.mutable_data(), z.data(), z.size() * sizeof(X));
+            return py::make_tuple(out, ifail);
+        };
+        if (type == "d") {
+            std::vector<double> z;
+            { py::gil_scoped_release r; stein<double>(d, e, w, z, ifail, o); }
+            return shaped(z);
+        }
+        std::vector<float> df(d.begin(), d.end()), ef(e.begin(), e.end()), wf(w.begin(), w.end()), z;
+        { py::gil_scoped_release r; stein<float>(df, ef, wf, z, ifail, o); }
+        return shaped(z);
+    });
     m.def("sturm_count", [](std::string type, std::vector<double> d, std::vector<double> e, std::vector<double> x,
                             py::dict opts) {
         if (type != "d" && type != "s") throw Exception("sturm_count: float32 or float64");

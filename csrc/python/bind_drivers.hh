@@ -268,6 +268,11 @@ void bind_drivers(py::module_& m, std::string const& s) {
         Options op = to_options(o); Matrix<T> Z = opt_mat(z); std::vector<R> L;
         { py::gil_scoped_release r; heev(A, L, Z, op); }
         return L; });
+    DEF("heevx", [=](HermitianMatrix<T>& A, py::object z, Range range, double vl, double vu, int64_t il, int64_t iu,
+                     py::dict o) {
+        Options op = to_options(o); Matrix<T> Z = opt_mat(z); std::vector<R> L;
+        { py::gil_scoped_release r; heevx(A, range, R(vl), R(vu), il, iu, L, Z, op); }
+        return L; });
     DEF("hegv", [=](int64_t itype, HermitianMatrix<T>& A, HermitianMatrix<T>& B, py::object z, py::dict o) {
         Options op = to_options(o); Matrix<T> Z = opt_mat(z); std::vector<R> L;
         { py::gil_scoped_release r; hegv(itype, A, B, L, Z, op); }
@@ -370,6 +375,11 @@ void bind_drivers(py::module_& m, std::string const& s) {
         DEF("syev", [=](SymmetricMatrix<T>& A, py::object z, py::dict o) {
             Options op = to_options(o); Matrix<T> Z = opt_mat(z); std::vector<R> L;
             { py::gil_scoped_release r; syev(A, L, Z, op); }
+            return L; });
+        DEF("syevx", [=](SymmetricMatrix<T>& A, py::object z, Range range, double vl, double vu, int64_t il,
+                         int64_t iu, py::dict o) {
+            Options op = to_options(o); Matrix<T> Z = opt_mat(z); std::vector<R> L;
+            { py::gil_scoped_release r; syevx(A, range, R(vl), R(vu), il, iu, L, Z, op); }
             return L; });
         DEF("sygv", [=](int64_t itype, SymmetricMatrix<T>& A, SymmetricMatrix<T>& B, py::object z, py::dict o) {
             Options op = to_options(o); Matrix<T> Z = opt_mat(z); std::vector<R> L;

@@ -205,6 +205,15 @@ int slate_hermitian_eig_##X(slate_Uplo uplo, slate_Matrix_##X A, X##_r* Lambda, 
     return guarded([&]() { slate::HermitianMatrix<T> H(slate::Uplo(uplo), A->A);                          \
         std::vector<X##_r> L; slate::Matrix<T> Zm = Z ? Z->A : slate::Matrix<T>();                         \
         slate::heev(H, L, Zm, to_opts(no, o)); std::copy(L.begin(), L.end(), Lambda); return 0; }, -1); }  \
+int slate_hermitian_eig_range_##X(slate_Uplo uplo, slate_Matrix_##X A, slate_Range range, X##_r vl,       \
+                                  X##_r vu, int64_t il, int64_t iu, int64_t* nfound, X##_r* Lambda,        \
+                                  slate_Matrix_##X Z, int no, slate_Options const* o) {                    \
+    return guarded([&]() { slate::HermitianMatrix<T> H(slate::Uplo(uplo), A->A);                          \
+        std::vector<X##_r> L; slate::Matrix<T> Zm = Z ? Z->A : slate::Matrix<T>();                         \
+        struct Fill { std::vector<X##_r>& L; X##_r* out; int64_t* nf;                                      \
+            ~Fill() { if (nf) *nf = int64_t(L.size()); if (out) std::copy(L.begin(), L.end(), out); } }    \
+            fill{L, Lambda, nfound};   /* Lambda is filled even when Z turns out too narrow */             \
+        slate::heevx(H, slate::Range(range), vl, vu, il, iu, L, Zm, to_opts(no, o)); return 0; }, -1); }   \
 int slate_svd_##X(slate_Matrix_##X A, X##_r* Sigma, slate_Matrix_##X U, slate_Matrix_##X VT, int no,      \
                   slate_Options const* o) {                                                                \
     return guarded([&]() { std::vector<X##_r> S;                                                          \
@@ -284,6 +293,35 @@ int slate_bdsbz_r32(slate_Range range, float vl, float vu, int64_t il, int64_t i
 int slate_bdsbz_r64(slate_Range range, double vl, double vu, int64_t il, int64_t iu, int64_t n, double const* d,
                     double const* e, int64_t* nfound, double* s, int no, slate_Options const* o) {
     return bisect_c<double>(true, range, vl, vu, il, iu, n, d, e, nfound, s, no, o);
+}
+}  // extern "C"
+
+namespace {
+template <typename R>
+int stein_c(int64_t n, R const* d, R const* e, int64_t m, R const* w, R* z, int64_t ldz, int64_t* nfailed,
+            int64_t* ifail, int no, slate_Options const* o) {
+    return guarded([&]() {
+        slate_error_if_msg(n < 0 || m < 0 || (n > 0 && !d) || (n > 1 && !e) || (m > 0 && !w),
+                           "stein: n < 0, m < 0 or a null array");
+        slate_error_if_msg(m > 0 && n > 0 && (!z || ldz < n), "stein: z is null or ldz < n");
+        std::vector<R> D(d, d + n), E(e, e + std::max<int64_t>(n - 1, 0)), W(w, w + m), Z;
+        std::vector<int64_t> bad;
+        slate::stein<R>(D, E, W, Z, bad, to_opts(no, o));
+        for (int64_t j = 0; j < m; ++j) std::copy(Z.begin() + j * n, Z.begin() + (j + 1) * n, z + j * ldz);
+        if (nfailed) *nfailed = int64_t(bad.size());
+        if (ifail) std::copy(bad.begin(), bad.end(), ifail);
+        return 0; }, -1);
+}
+}  // namespace
+
+extern "C" {
+int slate_stein_r32(int64_t n, float const* d, float const* e, int64_t m, float const* w, float* z, int64_t ldz,
+                    int64_t* nfailed, int64_t* ifail, int no, slate_Options const* o) {
+    return stein_c<float>(n, d, e, m, w, z, ldz, nfailed, ifail, no, o);
+}
+int slate_stein_r64(int64_t n, double const* d, double const* e, int64_t m, double const* w, double* z, int64_t ldz,
+                    int64_t* nfailed, int64_t* ifail, int no, slate_Options const* o) {
+    return stein_c<double>(n, d, e, m, w, z, ldz, nfailed, ifail, no, o);
 }
 }  // extern "C"
 

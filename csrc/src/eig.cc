@@ -748,13 +748,96 @@ void rescale_values(std::vector<R>& v, R anorm, R alpha) {
     for (auto& x : v) x = x / alpha * anorm;   // divide first: x / alpha stays in range
 }
 
+/// The tridiagonal stage of heev_body.  Null: heev's own, all pairs by divide
+/// and conquer or QR (or all values by sterf / stebz).  Set (heevx): the
+/// values of a range by stebz and, when Z is wanted, their vectors by stein;
+/// m is the number of values found.
+template <typename R>
+struct Subset {
+    Range range = Range::All;
+    R vl = 0, vu = 0;
+    int64_t il = 0, iu = 0;
+    int64_t m = 0;
+};
+
+/// slate::NotImplemented unless heevx can take this operand (one process,
+/// one device, block-cyclic), in the words of reduce_check_operand.
+template <typename T>
+void heevx_check_operand(BaseMatrix<T> const& A, char const* what) {
+    const std::string pre = "heevx: the subset driver ";
+    if (!A.storage()) return;
+    if (A.is_multi_device()) slate_not_implemented(pre + "runs on one device (" + what + " is a multi-device matrix)");
+    if (A.arbitrary_layout())
+        slate_not_implemented(pre + "needs a block-cyclic operand (" + what + " has a lambda layout)");
+    if (A.grid()->size() != 1)
+        slate_not_implemented(pre + "needs a grid of one process (" + what + " is distributed over " +
+                              std::to_string(A.grid()->size()) + "); a distributed stein is not implemented");
+}
+
+/// heevx's tridiagonal stage on the (d, e) of the scaled matrix: the values
+/// of the range into Lambda, rescaled, and their number into sub.m.  With a
+/// wanted Z (checked here: n rows, at least m columns) and m > 0 the stein
+/// vectors, n x m with leading dimension n, into Qs (memory of the target);
+/// returns whether Qs was filled.  Z is zeroed when it is wanted and m = 0.
+template <typename T>
+bool subset_stage(std::vector<real_type<T>>& d, std::vector<real_type<T>>& e, Subset<real_type<T>>& sub,
+                  real_type<T> anorm, real_type<T> alpha, std::vector<real_type<T>>& Lambda, Matrix<T>& Z,
+                  Work<real_type<T>>& Qs, Options const& opts) {
+    using R = real_type<T>;
+    const int64_t n = int64_t(d.size());
+    R vl = sub.vl, vu = sub.vu;
+    if (alpha != R(1)) { vl = vl / anorm * alpha; vu = vu / anorm * alpha; }   // the range of the scaled matrix
+    std::vector<R> W;
+    stebz<R>(sub.range, vl, vu, sub.il, sub.iu, d, e, W, opts);
+    const int64_t m = int64_t(W.size());
+    sub.m = m;
+    Lambda = W;
+    rescale_values(Lambda, anorm, alpha);
+    if (!wanted(Z)) return false;
+    slate_error_if_msg(Z.m() != n || Z.n() < m,
+                       "heevx: Z must have n = " + std::to_string(n) + " rows and at least m = " + std::to_string(m) +
+                           " columns, the number of eigenvalues found (it is " + std::to_string(Z.m()) + " x " +
+                           std::to_string(Z.n()) + ")");
+    if (m == 0) {
+        set(T(0), T(0), Z, opts);
+        return false;
+    }
+    const Target target = resolve_target(opts);
+    Qs.resize(target, size_t(n * m));
+    std::vector<int64_t> ifail;
+    stein_core<R>(d, e, W, Qs.data(), n, target == Target::Devices, ifail, opts);
+    return true;
+}
+
+/// Z(:, 0:m) = the n x m block at src (leading dimension lds, memory of the
+/// target), Z(:, m:) = 0; Z is a whole matrix of one process.
+template <typename T>
+void place_subset(Matrix<T>& Z, int64_t m, T const* src, int64_t lds, lb::Ctx const& c, Options const& opts) {
+    const int64_t n = Z.m();
+    slate_error_if_msg(Z.op() != Op::NoTrans || !Z.aligned(), "heevx: needs a whole NoTrans Z");
+    LocalBlock<T> lz = Z.local(c.dev() ? Loc::Device : Loc::Host, true);
+    slate_error_if_msg(lz.m != n || lz.n != Z.n(), "heevx: needs the whole of Z in one local block");
+    if (c.dev()) {
+        slate_hip_call(hipMemcpy2DAsync(lz.ptr, size_t(lz.ld) * sizeof(T), src, size_t(lds) * sizeof(T),
+                                        size_t(n) * sizeof(T), size_t(m), hipMemcpyDeviceToDevice, c.stream));
+        if (lz.n > m)
+            slate_hip_call(hipMemset2DAsync(lz.ptr + m * lz.ld, size_t(lz.ld) * sizeof(T), 0, size_t(n) * sizeof(T),
+                                            size_t(lz.n - m), c.stream));
+        slate_hip_call(hipStreamSynchronize(c.stream));
+    } else {
+        for (int64_t j = 0; j < lz.n; ++j)
+            for (int64_t i = 0; i < n; ++i) lz.ptr[i + j * lz.ld] = j < m ? src[i + j * lds] : T(0);
+    }
+    finish_origin(Z, opts);
+}
+
 /// heev with MethodHetrd::OneStage after the range guard: F holds the scaled
 /// lower triangle on a grid of one process.  hetrd on F's local block, then
 /// sterf, or the tridiagonal eigenvectors into Qt, copied to Z's layout and
 /// multiplied by Q panel by panel.
 template <typename R>
 void heev_one_stage(Matrix<R>& F, std::vector<R>& Lambda, Matrix<R>& Z, R anorm, R alpha, int64_t nb,
-                    Options const& opts) {
+                    Options const& opts, Subset<R>* sub) {
     const Target target = resolve_target(opts);
     const Loc loc = loc_of(target);
     const int64_t n = F.n();
@@ -766,6 +849,15 @@ void heev_one_stage(Matrix<R>& F, std::vector<R>& Lambda, Matrix<R>& Z, R anorm,
     {
         trace::Block t2("hetrd");
         hetrd_local<R>(c, n, lf.ptr, lf.ld, d, e, tau.data(), Tfac.data());
+    }
+    if (sub) {
+        // heevx: stein's n x m block, multiplied by Q in place, into Z
+        Work<R> Qs;
+        if (!subset_stage<R>(d, e, *sub, anorm, alpha, Lambda, Z, Qs, opts)) return;
+        trace::Block t2("unmtr_hetrd");
+        unmtr_hetrd_local<R>(c, Side::Left, Op::NoTrans, n, lf.ptr, lf.ld, Tfac.data(), n, sub->m, Qs.data(), n);
+        place_subset<R>(Z, sub->m, Qs.data(), n, c, opts);
+        return;
     }
     if (!wanted(Z)) {
         tridiag_values<R>(d, e, Lambda, opts);
@@ -812,19 +904,28 @@ void heev_one_stage(Matrix<R>& F, std::vector<R>& Lambda, Matrix<R>& Z, R anorm,
 }  // namespace
 
 template <typename T>
-void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts) {
+void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts);
+
+namespace {
+
+/// heev (sub null) and heevx (sub set) share everything but the tridiagonal
+/// stage and the width of the back-transform.
+template <typename T>
+void heev_body(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts,
+               Subset<real_type<T>>* sub) {
+    const char* const who = sub ? "heevx" : "heev";
     const int64_t mh = get_option<int64_t>(opts, Option::MethodHetrd, int64_t(MethodHetrd::TwoStage));
     slate_error_if_msg(mh != int64_t(MethodHetrd::TwoStage) && mh != int64_t(MethodHetrd::OneStage),
                        "heev: Option::MethodHetrd is neither MethodHetrd::TwoStage nor MethodHetrd::OneStage");
     const bool one_stage = mh == int64_t(MethodHetrd::OneStage);
-    if (wanted(Z) && eig_bisection(opts))
+    if (!sub && wanted(Z) && eig_bisection(opts))
         slate_not_implemented("heev: MethodEig::Bisection computes values only; eigenvectors of the bisection "
                               "values need inverse iteration, which is not implemented");
     if (one_stage) {
-        internal::hetrd_check_operand<T>(A, "heev", "A");
-        if (wanted(Z)) internal::hetrd_check_operand<T>(Z, "heev", "Z");
+        internal::hetrd_check_operand<T>(A, who, "A");
+        if (wanted(Z)) internal::hetrd_check_operand<T>(Z, who, "Z");
     }
-    {   // multi-device A (and Z): on its devices
+    if (!sub) {   // multi-device A (and Z): on its devices
         bool ran = internal::spread<T>(opts, {{&A, true}, {&Z, true}}, [&](std::vector<Matrix<T>>& M, int r) {
             auto H = internal::rewrap(A, M[0]);
             std::vector<real_type<T>> L;
@@ -833,14 +934,14 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
         }, false);
         if (ran) return;
     }
-    if (A.arbitrary_layout() || Z.arbitrary_layout()) {
+    if (!sub && (A.arbitrary_layout() || Z.arbitrary_layout())) {
         HermitianMatrix<T> Ab(A.uplo(), bc_operand(A, opts));
         Matrix<T> Zb = wanted(Z) ? block_cyclic(Z, opts) : Z;
         heev(Ab, Lambda, Zb, opts);
         if (wanted(Z)) slate::copy<T, T>(Zb, Z, opts);
         return;
     }
-    trace::Block tb("heev");
+    trace::Block tb(who);
     internal::DriverScope ds_;
     using R = real_type<T>;
     Target target = resolve_target(opts);
@@ -848,12 +949,13 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
     const int64_t n = A.n();
     Lambda.assign(n, R(0));
     if (n == 0) return;
+    if (sub) sub->m = sub->range == Range::Index ? sub->iu - sub->il + 1 : n;   // what a NaN / Inf matrix returns
     // range guard (reference heev.cc:73-102): the scaled copy F is reduced,
     // Lambda is rescaled at the end; eigenvectors are scale-invariant
     const R anorm = slate::norm(Norm::Max, A, opts);
     bool bad = false;
     const R alpha = range_alpha(anorm, bad);
-    if (bad) { Lambda.assign(n, anorm); return; }
+    if (bad) { Lambda.assign(sub ? sub->m : n, anorm); return; }
     // band width of the two-stage reduction: the bulge chase costs O(n^2 kd)
     // on the host, the first stage is memory-bound either way, so large tiles
     // are re-tiled to kd <= 64 (reference uses the tile size)
@@ -871,7 +973,7 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
     }
     if (alpha != R(1)) scale(alpha, anorm, F, opts);
     if (one_stage) {
-        if constexpr (!is_complex_v<T>) heev_one_stage(F, Lambda, Z, anorm, alpha, A.nb(), opts);
+        if constexpr (!is_complex_v<T>) heev_one_stage(F, Lambda, Z, anorm, alpha, A.nb(), opts, sub);
         return;
     }
     const int64_t nt = F.nt();
@@ -883,7 +985,7 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
     std::vector<R> d, e;
     host::Reflectors<T> Q2;
     std::vector<T> phase;
-    const bool ovl = wanted(Z) && eig_overlap(target, false) && nt >= 2;
+    const bool ovl = !sub && wanted(Z) && eig_overlap(target, false) && nt >= 2;   // heevx never forms the n x n Q
     Matrix<T> Q1x;   // explicit stage-1 Q (ovl)
     {
         trace::Block t2("hb2st");
@@ -906,6 +1008,43 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
         }
     }
     B.clear(); B.shrink_to_fit();
+    if (sub) {
+        // heevx: diag(phase) times stein's n x m block, then the two back-transforms on those m columns
+        Work<R> Qs;
+        if (!subset_stage<T>(d, e, *sub, anorm, alpha, Lambda, Z, Qs, opts)) return;
+        const int64_t m = sub->m;
+        Matrix<T> Zw(n, m, kd, kd, gA);
+        Zw.insertLocalTiles(target);
+        LocalBlock<T> lz = Zw.local(loc, true);
+        slate_error_if_msg(lz.m != n || lz.n != m, "heevx: needs the whole of its workspace in one local block");
+        lb::Ctx c = target == Target::Devices ? lb::Ctx::device(0) : lb::Ctx::host();
+        {
+            trace::Block t2("unmtr_hb2st");
+            if (c.dev()) {
+                Work<T> dph(Target::Devices, size_t(n));
+                device::memcpy_async(dph.data(), phase.data(), n * sizeof(T), c.stream);
+                slate_amd::dev::real_rowscale(n, m, Qs.data(), n, slate_amd::dev::dptr(dph.data()),
+                                              slate_amd::dev::dptr(lz.ptr), lz.ld, c.stream);
+                slate_hip_call(hipStreamSynchronize(c.stream));
+            } else {
+                for (int64_t j = 0; j < m; ++j)
+                    for (int64_t i = 0; i < n; ++i) lz.ptr[i + j * lz.ld] = phase[i] * T(Qs.data()[i + j * n]);
+            }
+            Comm& w = gA->world();
+            stage2_apply(Q2, stage2_streamed<T>(target, kd, w), n, kd, lz.ptr, lz.ld, m, c, w);
+        }
+        {
+            trace::Block t3("unmtr_he2hb");
+            if (nt >= 2) {
+                Matrix<T> P = F.sub(1, nt - 1, 0, nt - 2);
+                Matrix<T> Zs = Zw.sub(1, nt - 1, 0, Zw.nt() - 1);
+                unmqr(Side::Left, Op::NoTrans, P, stacked_T(Ts, nt - 1, F.nb(), P.n(), opts), Zs, opts);
+            }
+        }
+        LocalBlock<T> lw = Zw.local(loc, false);
+        place_subset<T>(Z, m, lw.ptr, lw.ld, c, opts);
+        return;
+    }
     if (!wanted(Z)) {
         tridiag_values<R>(d, e, Lambda, opts);
         rescale_values(Lambda, anorm, alpha);
@@ -986,6 +1125,32 @@ void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
     }
     slate::copy<T, T>(Zw, Z, opts);
     (void)loc;
+}
+
+}  // namespace
+
+template <typename T>
+void heev(HermitianMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts) {
+    heev_body<T>(A, Lambda, Z, opts, nullptr);
+}
+
+template <typename T>
+int64_t heevx(HermitianMatrix<T>& A, Range range, real_type<T> vl, real_type<T> vu, int64_t il, int64_t iu,
+              std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts) {
+    using R = real_type<T>;
+    heevx_check_operand<T>(A, "A");
+    if (wanted(Z)) heevx_check_operand<T>(Z, "Z");
+    slate_error_if_msg(range != Range::All && range != Range::Value && range != Range::Index,
+                       "heevx: range is none of Range::All, Range::Value, Range::Index");
+    if (range == Range::Value) slate_error_if_msg(!(vl < vu), "heevx: Range::Value needs vl < vu");
+    if (range == Range::Index)
+        slate_error_if_msg(il < 1 || iu < il || iu > A.n(), "heevx: Range::Index needs 1 <= il <= iu <= n");
+    Subset<R> sub;
+    sub.range = range;
+    sub.vl = vl; sub.vu = vu;
+    sub.il = il; sub.iu = iu;
+    heev_body<T>(A, Lambda, Z, opts, &sub);
+    return sub.m;
 }
 
 //------------------------------------------------------------------------------
@@ -1449,6 +1614,8 @@ void svd_square(Matrix<T>& A, std::vector<real_type<T>>& Sigma, Matrix<T>& U, Ma
 #define SLATE_EIG_INST(T)                                                                                   \
     template void he2hb<T>(Matrix<T>&, std::vector<TriangularFactors<T>>&, Options const&);                 \
     template void heev<T>(HermitianMatrix<T>&, std::vector<real_type<T>>&, Matrix<T>&, Options const&);     \
+    template int64_t heevx<T>(HermitianMatrix<T>&, Range, real_type<T>, real_type<T>, int64_t, int64_t,     \
+                              std::vector<real_type<T>>&, Matrix<T>&, Options const&);                      \
     template void hegst<T>(int64_t, HermitianMatrix<T>&, HermitianMatrix<T> const&, Options const&);        \
     template void hegv<T>(int64_t, HermitianMatrix<T>&, HermitianMatrix<T>&, std::vector<real_type<T>>&,    \
                           Matrix<T>&, Options const&);                                                      \

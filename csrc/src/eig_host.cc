@@ -2,6 +2,7 @@
 #include "slate_amd/eig_host.hh"
 #include "slate_amd/host_blas.hh"
 #include "slate_amd/secular.hh"
+#include "slate_amd/stein.hh"
 #include "slate_amd/sturm.hh"
 #include "slate_amd/exception.hh"
 
@@ -1000,7 +1001,100 @@ int64_t stebz_range(int64_t n, const R* d, const R* e2, R pivmin, R lo, R hi, R 
 SLATE_STEBZ_HOST_INST(float)
 SLATE_STEBZ_HOST_INST(double)
 
-#define SLATE_EIGH_INST(T)                                                                              \
+//------------------------------------------------------------------------------
+// Inverse iteration: host twin of kernels/stein.hip (slate_amd/stein.hh)
+template <typename R>
+void stein(int64_t n, const R* d, const R* e, R onenrm, int64_t m, const R* w, const int32_t* cluster,
+           int64_t nclusters, const int64_t* first, const int64_t* last, R* Z, int64_t ldz, int32_t* done) {
+    namespace st = slate::invit;
+    if (n <= 0 || m <= 0) return;
+    const R bn = st::rhs_norm<R>(n, onenrm);
+    std::vector<R> binf(size_t(m), R(1)), unn(size_t(m), R(0)), xm(size_t(m), R(0));
+    std::vector<int32_t> pass(size_t(m), 0), cpass(size_t(nclusters), 0), cdone(size_t(nclusters), 0);
+    std::fill(done, done + m, 0);
+    const bool par = m * n > 4096;
+    #pragma omp parallel for schedule(static) if (par)
+    for (int64_t j = 0; j < m; ++j)
+        for (int64_t i = 0; i < n; ++i) Z[i + j * ldz] = st::start_entry<R>(i, j);
+    // x (unit 2-norm or the start vector), its entry of largest modulus xm, after a scaling by 1 / nrm
+    auto normalise = [&](int64_t j, R xmax, R sumsq) {
+        const R nrm = std::sqrt(sumsq);
+        R* x = Z + j * ldz;
+        if (nrm > R(0)) {
+            const R r = R(1) / nrm;
+            for (int64_t i = 0; i < n; ++i) x[i] *= r;
+            xmax *= r;
+        }
+        xm[j] = xmax;
+        binf[j] = std::abs(xmax) > R(0) ? std::abs(xmax) : R(1);
+    };
+    for (int round = 0; round < st::kRounds; ++round) {
+        #pragma omp parallel if (par)
+        {
+            std::vector<R> u(size_t(3 * n));
+            #pragma omp for schedule(dynamic, 4)
+            for (int64_t j = 0; j < m; ++j) {
+                if (done[j]) continue;
+                R xmax, sumsq;
+                unn[j] = st::solve_round<R>(n, d, e, w[j], bn / binf[j], Z + j * ldz, u.data(), u.data() + n,
+                                            u.data() + 2 * n, xmax, sumsq);
+                if (cluster[j] >= 0) continue;   // judged after the orthonormalisation
+                pass[j] += st::grown<R>(xmax, unn[j], n);
+                done[j] = pass[j] >= st::kAccept;
+                normalise(j, xmax, sumsq);
+            }
+        }
+        // classical Gram-Schmidt, applied twice, in value order; a cluster finishes as a whole
+        #pragma omp parallel for schedule(dynamic, 1) if (par && nclusters > 1)
+        for (int64_t c = 0; c < nclusters; ++c) {
+            if (cdone[c]) continue;
+            bool ok = true;
+            std::vector<R> h;
+            for (int64_t j = first[c]; j <= last[c]; ++j) {
+                R* x = Z + j * ldz;
+                const int64_t np = j - first[c];
+                h.resize(size_t(np));
+                for (int pass2 = 0; pass2 < 2 && np > 0; ++pass2) {
+                    for (int64_t p = 0; p < np; ++p) {
+                        const R* q = Z + (first[c] + p) * ldz;
+                        R s = R(0);
+                        for (int64_t i = 0; i < n; ++i) s += q[i] * x[i];
+                        h[p] = s;
+                    }
+                    for (int64_t p = 0; p < np; ++p) {
+                        const R* q = Z + (first[c] + p) * ldz;
+                        for (int64_t i = 0; i < n; ++i) x[i] -= h[p] * q[i];
+                    }
+                }
+                R xmax = R(0), sumsq = R(0);
+                for (int64_t i = n - 1; i >= 0; --i) {
+                    if (std::abs(x[i]) >= std::abs(xmax)) xmax = x[i];
+                    sumsq += x[i] * x[i];
+                }
+                ok = ok && st::grown<R>(xmax, unn[j], n);
+                normalise(j, xmax, sumsq);
+            }
+            cpass[c] += ok;
+            if (cpass[c] >= st::kAccept) {
+                cdone[c] = 1;
+                for (int64_t j = first[c]; j <= last[c]; ++j) done[j] = 1;
+            }
+        }
+    }
+    // the entry of largest modulus positive
+    #pragma omp parallel for schedule(static) if (par)
+    for (int64_t j = 0; j < m; ++j)
+        if (xm[j] < R(0))
+            for (int64_t i = 0; i < n; ++i) Z[i + j * ldz] = -Z[i + j * ldz];
+}
+
+#define SLATE_STEIN_HOST_INST(R)                                                                        \
+    template void stein<R>(int64_t, const R*, const R*, R, int64_t, const R*, const int32_t*, int64_t,  \
+                           const int64_t*, const int64_t*, R*, int64_t, int32_t*);
+SLATE_STEIN_HOST_INST(float)
+SLATE_STEIN_HOST_INST(double)
+
+#define SLATE_EIGH_INST(T)                                                                           \
     template struct Reflectors<T>;                                                                     \
     template void hb2st<T>(int64_t, int64_t, T*, int64_t, std::vector<real_type<T>>&,                   \
                            std::vector<real_type<T>>&, Reflectors<T>&, std::vector<T>&);                \

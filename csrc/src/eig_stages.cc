@@ -365,6 +365,14 @@ void syev(SymmetricMatrix<T>& A, std::vector<real_type<T>>& Lambda, Matrix<T>& Z
 }
 
 template <typename T>
+int64_t syevx(SymmetricMatrix<T>& A, Range range, real_type<T> vl, real_type<T> vu, int64_t il, int64_t iu,
+              std::vector<real_type<T>>& Lambda, Matrix<T>& Z, Options const& opts) {
+    static_assert(!is_complex_v<T>, "syevx: real types only (use heevx)");
+    HermitianMatrix<T> H(A.uplo(), A);
+    return heevx(H, range, vl, vu, il, iu, Lambda, Z, opts);
+}
+
+template <typename T>
 void sygst(int64_t itype, SymmetricMatrix<T>& A, SymmetricMatrix<T> const& B, Options const& opts) {
     static_assert(!is_complex_v<T>, "sygst: real types only (use hegst)");
     HermitianMatrix<T> HA(A.uplo(), A), HB(B.uplo(), B);
@@ -472,6 +480,8 @@ void gels_cholqr(Matrix<T>& A, Matrix<T>& R, Matrix<T>& BX, Options const& opts)
                                    Matrix<T>&, Options const&);                                               \
     template void stedc_merge<T>(Matrix<T>&, Matrix<T>&, Matrix<T>&, Options const&);                         \
     template void syev<T>(SymmetricMatrix<T>&, std::vector<T>&, Matrix<T>&, Options const&);                  \
+    template int64_t syevx<T>(SymmetricMatrix<T>&, Range, T, T, int64_t, int64_t, std::vector<T>&, Matrix<T>&, \
+                              Options const&);                                                               \
     template void sygst<T>(int64_t, SymmetricMatrix<T>&, SymmetricMatrix<T> const&, Options const&);          \
     template void sygv<T>(int64_t, SymmetricMatrix<T>&, SymmetricMatrix<T>&, std::vector<T>&, Matrix<T>&,    \
                           Options const&);                                                                    \

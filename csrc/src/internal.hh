@@ -112,6 +112,15 @@ private:
     std::vector<T> h_;
 };
 
+/// stein after the public wrappers (stein.cc): the unit eigenvectors of
+/// tridiag(D, E) for the ascending values W into Z (n x m, column-major,
+/// leading dimension ldz), which is host memory, or with z_on_device (target
+/// Devices only) memory of the calling context's device, where heevx goes on
+/// with it.  ifail: the 1-based indices of the vectors that were not accepted.
+template <typename R>
+void stein_core(std::vector<R> const& D, std::vector<R> const& E, std::vector<R> const& W, R* Z, int64_t ldz,
+                bool z_on_device, std::vector<int64_t>& ifail, Options const& opts);
+
 /// Location of a target.
 inline Loc loc_of(Target t) { return t == Target::Devices ? Loc::Device : Loc::Host; }
 

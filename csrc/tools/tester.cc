@@ -1248,6 +1248,91 @@ Result r_bisect(Case<T>& c, bool bidiagonal) {
     return r;
 }
 
+/// stein on the tridiagonal of r_tridiag with stebz's values:
+/// r = max|T Z - Z diag(W)| / (n eps max|T_ij|), o = max|Z^T Z - I| / (n eps),
+/// accumulated in double; the error is max(r, o) eps.
+template <typename T>
+Result r_stein(Case<T>& c) {
+    using R = R_<T>;
+    const int64_t n = c.n;
+    std::vector<R> d(n), e(std::max<int64_t>(n - 1, 0)), w, z;
+    for (int64_t i = 0; i < n; ++i) d[i] = R(2) + R(i % 7) / R(10);
+    for (int64_t i = 0; i + 1 < n; ++i) e[i] = R(-1) + R(i % 5) / R(20);
+    stebz<R>(Range::All, R(0), R(0), 0, 0, d, e, w, c.opts);
+    Result r;
+    int64_t failed = 0;
+    r.time = c.timed([&] { failed = stein<R>(d, e, w, z, c.opts); });
+    r.flops = 0;
+    if (!c.P.check) return r;
+    const int64_t m = int64_t(w.size());
+    if (m != n || int64_t(z.size()) != n * m || failed) { r.error = double(n); return r; }
+    double tmax = 0, rr = 0, oo = 0;
+    for (R v : d) tmax = std::max(tmax, std::abs(double(v)));
+    for (R v : e) tmax = std::max(tmax, std::abs(double(v)));
+    #pragma omp parallel for reduction(max : rr, oo)
+    for (int64_t j = 0; j < m; ++j) {
+        const R* x = z.data() + j * n;
+        for (int64_t i = 0; i < n; ++i) {
+            double t = (double(d[i]) - double(w[j])) * double(x[i]);
+            if (i > 0) t += double(e[i - 1]) * double(x[i - 1]);
+            if (i + 1 < n) t += double(e[i]) * double(x[i + 1]);
+            rr = std::max(rr, std::abs(t));
+        }
+        for (int64_t k = 0; k <= j; ++k) {
+            const R* y = z.data() + k * n;
+            double dot = 0;
+            for (int64_t i = 0; i < n; ++i) dot += double(x[i]) * double(y[i]);
+            oo = std::max(oo, std::abs(dot - (k == j ? 1.0 : 0.0)));
+        }
+    }
+    const double ep = double(std::numeric_limits<R>::epsilon());
+    rr /= double(n) * ep * tmax;
+    oo /= double(n) * ep;
+    r.error = std::max(rr, oo) * ep;
+    char note[64];
+    std::snprintf(note, sizeof(note), "r=%.3f o=%.3f", rr, oo);
+    r.note = note;
+    return r;
+}
+
+/// heevx for the index range 1 .. max(1, n / 10): ||A Z - Z Lambda|| / (n ||A||)
+/// and ||Z^H Z - I|| / n; the error is the larger.
+template <typename T>
+Result r_heevx(Case<T>& c) {
+    if (is_complex_v<T> &&
+        get_option<int64_t>(c.opts, Option::MethodHetrd, int64_t(MethodHetrd::TwoStage)) == int64_t(MethodHetrd::OneStage)) {
+        Result r; r.skipped = true; r.note = "real types (the one-stage reduction)"; return r;
+    }
+    auto Ag = c.mat(c.n, c.n, "spd", 0.0);
+    auto A0 = c.copy_of(Ag);
+    HermitianMatrix<T> A(Uplo::Lower, Ag);
+    const int64_t iu = std::max<int64_t>(1, c.n / 10);
+    auto Z = c.zeros(c.n, iu);
+    std::vector<R_<T>> L;
+    int64_t m = 0;
+    Result r;
+    r.time = c.timed([&] { m = heevx(A, Range::Index, R_<T>(0), R_<T>(0), 1, iu, L, Z, c.opts); });
+    r.flops = cfac<T>() * 4.0 / 3 * double(c.n) * c.n * c.n;
+    if (!c.P.check) return r;
+    if (m != iu || int64_t(L.size()) != iu) { r.error = double(c.n); return r; }
+    auto AZ = c.zeros(c.n, iu), ZL = c.copy_of(Z);
+    gemm(T(1), A0, Z, T(0), AZ, c.opts);
+    std::vector<R_<T>> ones(c.n, R_<T>(1));
+    scale_row_col(Equed::Col, ones, L, ZL, c.opts);
+    add(T(-1), ZL, T(1), AZ, c.opts);
+    const double res = c.nrm(AZ) / (double(c.n) * c.nrm(A0));
+    auto G = c.zeros(iu, iu);
+    set(T(0), T(1), G, c.opts);
+    auto ZH = conj_transpose(Z);
+    gemm(T(1), ZH, Z, T(-1), G, c.opts);
+    const double orth = c.nrm(G) / double(c.n);
+    r.error = std::max(res, orth);
+    char note[96];
+    std::snprintf(note, sizeof(note), "m=%lld resid=%.2e orth=%.2e", (long long)m, res, orth);
+    r.note = note;
+    return r;
+}
+
 template <typename T>
 Result r_aux(Case<T>& c, int variant) {   // 0 add, 1 copy, 2 scale, 3 set, 4 trtrm, 5 colnorms, 6 henorm, 7 redistribute
     auto A = c.mat(c.m, c.n, "rands", -1, true), B = c.mat(c.m, c.n);
@@ -2115,6 +2200,8 @@ std::map<std::string, Fn<T>> routines() {
         {"steqr2", [](Case<T>& c) { return r_tridiag<T>(c, 1); }},
         {"stebz", [](Case<T>& c) { return r_bisect<T>(c, false); }},
         {"bdsbz", [](Case<T>& c) { return r_bisect<T>(c, true); }},
+        {"stein", [](Case<T>& c) { return r_stein<T>(c); }},
+        {"heevx", r_heevx<T>},
         {"add", [](Case<T>& c) { return r_aux<T>(c, 0); }},
         {"copy", [](Case<T>& c) { return r_aux<T>(c, 1); }},
         {"scale", [](Case<T>& c) { return r_aux<T>(c, 2); }},
@@ -2206,7 +2293,7 @@ int run_type(Params const& P, char tc, std::string const& name) {
                 const bool with_method_eig =
                     P.has_method_eig && (name == "heev" || name == "heev_vals");
                 if (with_method_eig) c.opts[Option::MethodEig] = P.method_eig;
-                const bool with_method_hetrd = P.has_method_hetrd && name == "heev";
+                const bool with_method_hetrd = P.has_method_hetrd && (name == "heev" || name == "heevx");
                 if (with_method_hetrd) c.opts[Option::MethodHetrd] = P.method_hetrd;
                 const bool with_method_gebrd = P.has_method_gebrd && (name == "svd" || name == "svd_vals");
                 if (with_method_gebrd) c.opts[Option::MethodGebrd] = P.method_gebrd;

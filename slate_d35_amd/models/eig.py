@@ -6,7 +6,8 @@ from ._wrap import call
 __all__ = ["heev", "hegv", "hegst", "svd", "svd_vals", "gesvd", "eig", "eig_vals", "he2hb", "hb2st", "sterf",
            "steqr", "stedc", "ge2tb", "tb2bd", "bdsqr", "syev", "sygv", "hb2st_band", "unmtr_hb2st",
            "unmtr_he2hb", "tb2bd_band", "unmbr_tb2bd", "unmbr_ge2tb", "steqr2", "stedc_matrix", "bdsqr_matrix",
-           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd", "gebrd", "unmbr_gebrd", "stebz", "bdsbz"]
+           "bdsdc", "bdsdc_matrix", "hetrd", "unmtr_hetrd", "gebrd", "unmbr_gebrd", "stebz", "bdsbz",
+           "stein", "heevx", "syevx"]
 
 
 def heev(A, Z=None, target=None, **kw):
@@ -67,15 +68,9 @@ def sterf(d, e, **kw):
     return _slate.sterf(list(d), list(e))
 
 
-def _bisect(bidiagonal, d, e, range, vl, vu, il, iu, target, kw):
-    import numpy as np
-    from .. import _slate
-    from .._core import Range, opts
-    d = np.asarray(d)
-    e = np.asarray(e)
-    dt = np.result_type(d.dtype, e.dtype) if e.size else d.dtype
-    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-        dt = np.dtype(np.float64)
+def _range(range, vl, vu, il, iu):
+    """(Range, vl, vu, il, iu) of the range arguments of stebz / bdsbz / heevx."""
+    from .._core import Range
     if not isinstance(range, Range):
         try:
             range = {"all": Range.All, "a": Range.All, "value": Range.Value, "v": Range.Value,
@@ -86,10 +81,22 @@ def _bisect(bidiagonal, d, e, range, vl, vu, il, iu, target, kw):
         raise ValueError("range=\"value\" needs vl and vu")
     if range == Range.Index and (il is None or iu is None):
         raise ValueError("range=\"index\" needs il and iu")
+    return (range, float(0 if vl is None else vl), float(0 if vu is None else vu),
+            int(0 if il is None else il), int(0 if iu is None else iu))
+
+
+def _bisect(bidiagonal, d, e, range, vl, vu, il, iu, target, kw):
+    import numpy as np
+    from .. import _slate
+    from .._core import opts
+    d = np.asarray(d)
+    e = np.asarray(e)
+    dt = np.result_type(d.dtype, e.dtype) if e.size else d.dtype
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        dt = np.dtype(np.float64)
+    range, vl, vu, il, iu = _range(range, vl, vu, il, iu)
     return _slate.stebz("s" if dt == np.float32 else "d", bidiagonal, range,
-                        float(0 if vl is None else vl), float(0 if vu is None else vu),
-                        int(0 if il is None else il), int(0 if iu is None else iu),
-                        d.astype(np.float64).tolist(), e.astype(np.float64).tolist(), opts(target, **kw))
+                        vl, vu, il, iu, d.astype(np.float64).tolist(), e.astype(np.float64).tolist(), opts(target, **kw))
 
 
 def stebz(d, e, range="all", vl=None, vu=None, il=None, iu=None, target=None, **kw):
@@ -109,6 +116,47 @@ def bdsbz(d, e, range="all", vl=None, vu=None, il=None, iu=None, target=None, **
     sqrt(safe_min) max|B|.  "index" counts from the largest (il = 1); the
     signs of d and e do not matter.  Arguments as for stebz."""
     return _bisect(True, d, e, range, vl, vu, il, iu, target, kw)
+
+
+def stein(d, e, w, target=None, **kw):
+    """Unit eigenvectors (ndarray n x m of d's precision, one column per
+    value) of the symmetric tridiagonal (d, e) for the m ascending eigenvalues
+    w, as stebz returns them, by inverse iteration: five rounds, clusters
+    (values closer than 1e-3 |T|_1) orthonormalised after each.  target="d"
+    runs the gfx950 kernels (launches that depend on n, m and the existence of
+    a cluster only, one host synchronisation, reproducible bits), the host
+    targets the same arithmetic with OpenMP.  ops.stein_stats() has the
+    counters, among them `failed`.  Raises on non-finite entries, a w that is
+    not ascending or more values than rows."""
+    import numpy as np
+    from .. import _slate
+    from .._core import opts
+    d = np.asarray(d)
+    e = np.asarray(e)
+    dt = np.result_type(d.dtype, e.dtype) if e.size else d.dtype
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        dt = np.dtype(np.float64)
+    z, _ = _slate.stein("s" if dt == np.float32 else "d", d.astype(np.float64).tolist(),
+                        e.astype(np.float64).tolist(), np.asarray(w, np.float64).tolist(), opts(target, **kw))
+    return z
+
+
+def heevx(A, Z=None, range="all", vl=None, vu=None, il=None, iu=None, target=None, **kw):
+    """Eigenvalues of a range (ascending numpy array of m values; the range
+    arguments of stebz) of a Hermitian matrix and, when Z is given (n rows, at
+    least m columns), their eigenvectors in its first m columns, the others
+    zero: the reduction of method_hetrd ("two_stage", default, or "one_stage",
+    real types), stebz, stein, and the back-transforms on m columns only.  A
+    is not modified.  One process, one device."""
+    import numpy as np
+    return np.asarray(call("heevx", A, A, Z, *_range(range, vl, vu, il, iu), target=target, **kw))
+
+
+def syevx(A, Z=None, range="all", vl=None, vu=None, il=None, iu=None, target=None, **kw):
+    """heevx for a real SymmetricMatrix (a HermitianMatrix is accepted too)."""
+    import numpy as np
+    name = "syevx" if type(A).__name__.startswith("SymmetricMatrix") else "heevx"
+    return np.asarray(call(name, A, A, Z, *_range(range, vl, vu, il, iu), target=target, **kw))
 
 
 def steqr(d, e, Z=None, **kw):

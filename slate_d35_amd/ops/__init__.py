@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from .. import _slate
 
-__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "geqp3_stats", "gemv_t_block", "gemv_n_block", "herk", "gemm_tri", "gemm_variant_counts", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
+__all__ = ["have_native_ops", "gemm", "gemm_async", "gemm_lowprec", "lowprec_gemm_calls", "bdsdc_stats", "sturm_count", "stebz_stats", "stein_stats", "symv_lower", "hetrd_stats", "gebrd_stats", "geqp3_stats", "gemv_t_block", "gemv_n_block", "herk", "gemm_tri", "gemm_variant_counts", "trsm", "potrf", "getrf_panel", "geqrf_panel", "lu_sign",
            "set_queue", "queue_sync"]
 
 
@@ -101,6 +101,17 @@ def sturm_count(d, e, x, target=None):
     t = "s" if d.dtype == np.float32 else "d"
     as_list = lambda a: np.asarray(a).astype(np.float64).ravel().tolist()
     return _slate.sturm_count(t, as_list(d), as_list(e), as_list(x), opts(target))
+
+
+def stein_stats() -> dict:
+    """Counters of the last stein of this process (also through heevx): `n`,
+    `values` (vectors), `clusters` and `largest_cluster`, `rounds` (always
+    five), `failed` (vectors that never passed the growth test), `launches`
+    and `host_syncs` (both zero on the host targets); with
+    SLATE_STEIN_PROFILE=1 in the environment also `ms_solve`, `ms_orth` and
+    `ms_transpose`, the device time by kernel."""
+    from .. import _slate
+    return _slate.stein_stats()
 
 
 def stebz_stats() -> dict:

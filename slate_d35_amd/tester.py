@@ -87,7 +87,7 @@ class Ctx:
 
     def method_hetrd(self):
         mh = getattr(self.a, "method_hetrd", None)
-        return mh if mh and self.name == "heev" else None
+        return mh if mh and self.name in ("heev", "heevx") else None
 
     def method_gebrd(self):
         mg = getattr(self.a, "method_gebrd", None)
@@ -472,6 +472,47 @@ def r_bdsbz(c):
     return _bisect(c, True)
 
 
+def r_stein(c):
+    """stein on the tridiagonal of stebz with that routine's values:
+    r = max|T Z - Z diag(W)| / (n eps max|T_ij|) and o = max|Z^T Z - I| / (n eps);
+    the error is max(r, o) eps."""
+    _real_only(c)
+    n = c.n
+    i = np.arange(n)
+    d = (2 + (i % 7) / 10).astype(c.dt)
+    e = (-1 + (i[:max(n - 1, 0)] % 5) / 20).astype(c.dt)
+    w = M.stebz(d, e, target=c.target)
+    t, z = _timed(lambda: M.stein(d, e, w, target=c.target))
+    if not c.a.check:
+        return t, None
+    from . import ops
+    if z.shape != (n, n) or ops.stein_stats()["failed"]:
+        return t, float(n)
+    ep = float(np.finfo(c.dt).eps)
+    T, Z, W = _tridiag(d, e).astype(np.float64), z.astype(np.float64), w.astype(np.float64)
+    r = np.abs(T @ Z - Z * W).max() / (n * ep * np.abs(T).max())
+    o = np.abs(Z.T @ Z - np.eye(n)).max() / (n * ep)
+    return t, max(r, o) * ep, f"r={r:.3f} o={o:.3f}"
+
+
+def r_heevx(c):
+    """heevx for the index range 1 .. max(1, n / 10): ||A Z - Z Lambda|| /
+    (n ||A||) and ||Z^H Z - I|| / n; the error is the larger."""
+    a, A = c.mat(c.n, c.n, "spd")
+    H = core.HermitianMatrix(core.Uplo.Lower, A)
+    iu = max(1, c.n // 10)
+    Z = core.from_numpy(np.zeros((c.n, iu), c.dt), nb=c.nb, target=c.target)
+    t, w = _timed(lambda: M.heevx(H, Z, range="index", il=1, iu=iu, **c.opts()))
+    if not c.a.check:
+        return t, None
+    if len(w) != iu:
+        return t, float(c.n)
+    z = core.to_numpy(Z)
+    res = np.linalg.norm(a @ z - z * w) / (np.linalg.norm(a) * c.n)
+    orth = np.linalg.norm(z.conj().T @ z - np.eye(iu)) / c.n
+    return t, max(res, orth), f"m={iu} resid={res:.2e} orth={orth:.2e}"
+
+
 def r_hesv(c):
     a, A = c.mat(c.n, c.n)
     a = (a + a.conj().T) / 2
@@ -538,6 +579,8 @@ ROUTINES = {
     "svd_vals": (r_svd_vals, lambda m, n, k: 8.0 / 3.0 * n ** 3),
     "stebz": (r_stebz, lambda m, n, k: 0.0),
     "bdsbz": (r_bdsbz, lambda m, n, k: 0.0),
+    "stein": (r_stein, lambda m, n, k: 0.0),
+    "heevx": (r_heevx, lambda m, n, k: 4.0 / 3.0 * n ** 3),
     "hetrd": (r_hetrd, lambda m, n, k: 4.0 / 3.0 * n ** 3),
     "unmtr_hetrd": (r_unmtr_hetrd, lambda m, n, k: 0.0),
     "gebrd": (r_gebrd, lambda m, n, k: 4.0 * m * n * n - 4.0 / 3.0 * n ** 3),
@@ -603,11 +646,11 @@ def main(argv=None):
                     for _ in range(a.repeat):
                         c = Ctx(a, dt, dim, nb, name)
                         try:
-                            t, err = fn(c)
+                            t, err, *note = fn(c)   # a routine may add a note to its row
                             ok = err is None or err <= a.tol * eps(dt)
                             status = "pass" if ok else "FAILED"
                         except NotImplementedError as e:  # precision not provided (e.g. mixed for s/c)
-                            t, err, status = float("nan"), None, f"skip ({e})"
+                            t, err, note, status = float("nan"), None, [], f"skip ({e})"
                             ok = True
                         nfail += 0 if ok else 1
                         gf = fl(c.m, c.n, c.k) / t / 1e9 if t == t and t > 0 else float("nan")
@@ -615,6 +658,7 @@ def main(argv=None):
                             es = "NA" if err is None else f"{err:.2e}"
                             print(f"{name:18s} {tch:4s} {c.m:6d} {c.n:6d} {c.k:6d} {nb:5d} {p:2d} {q:2d} "
                                   f"{es:>10s} {t:10.4f} {gf:10.2f}  {status}"
+                                  + (f"  {note[0]}" if note else "")
                                   + (f"  gemm_precision={c.gemm_precision()}" if c.gemm_precision() else "")
                                   + (f"  method_svd={c.method_svd()}" if c.method_svd() else "")
                                   + (f"  method_eig={c.method_eig()}" if c.method_eig() else "")
